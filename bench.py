@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: MDViT (adapt_method='Sup', MLPFM peer heads) train step at 512x512 on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B] [--size S] [--model mdvit|base]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--size S] [--model mdvit|base] [--dump-outputs DIR] [--full]
 
 One step = for each of the 4 domains a forward of B synthetic images, the fused BCE/Dice/KT losses and
 the reference's two-sweep backward (multi_train_MDViT.py:129-207), gradient all-reduce across ranks,
 AdamW update.  drop_rate = drop_path_rate = 0.1 as in multi_train_MDViT.py:59.  Inputs are resident in
 HBM before the timed region.  Rank 0 prints ONE JSON line (see README/DESIGN for the fields).
+
+A plain run sets up, runs W warm-up and K timed steps and prints the line.  --full adds everything else the
+line has carried: host settling, the per-kernel roofline, the fwd / bwd / optimizer split, the CPU baseline
+and the extra legs (bs=32, bf16, BASE, TransFuse, the block roofline at bs=32).
 """
 from __future__ import annotations
 
@@ -51,7 +55,7 @@ def parse():
     ap.add_argument("--reference-sweeps", action="store_true", help="run the reference's literal two full sweeps instead of the merged (linear-algebra-equivalent) form")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--settle-seconds", type=float, default=60.0,
-                    help="untimed settling before the warm-up steps: repeat the step until the host's enqueue time is stable (a fresh box pages the image in); 0: off")
+                    help="(--full) untimed settling before the warm-up steps: repeat the step until the host's enqueue time is stable (a fresh box pages the image in); 0: off")
     ap.add_argument("--by-shape", action="store_true", help="key the GEMM event table by (variant, M, N, K) -- for tools/gemm_shapes.py")
     ap.add_argument("--detail", default="", help="write the per-kernel table to this JSON file")
     ap.add_argument("--max-inflight", type=int, default=0,
@@ -60,8 +64,17 @@ def parse():
                          "cross-stream tensors in the RESERVED pool (bs=32: 105.9 GiB reserved with 1, 116.5 with 2; peak allocated 86.9 GiB either way since "
                          "ops._side_protect bounds what the weight-gradient stream holds)")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the bs=32 leg and the MHSA+DA block roofline at bs=32 that the default N=1 run appends to its JSON line")
+                    help="skip the bs=32 leg and the MHSA+DA block roofline at bs=32 that the --full N=1 run appends to its JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="also settle the host, time the dominant kernel against its roofline (--by-shape / --detail / MDVIT_BENCH_GEMM_SHAPES need it), "
+                         "split the step into fwd / bwd / optimizer, run the CPU baseline and the extra legs (each of these keeps its --no-* switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy: the step's returned losses, the updated float buffers "
+                         "and a fixed seeded sample of 2^23 updated parameter values (all of them when there are fewer).  Settling is skipped: the "
+                         "dumped state depends on how many steps ran")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.max_inflight <= 0:
         args.max_inflight = 2 if args.batch < 16 else 1
     return args
@@ -191,6 +204,32 @@ def cpu_baseline(size: int, budget_s: float = 40.0):
             "mdvit_1img": mdvit, "mdvit_1img_all_physical_cores": mdvit_all, "mdvit_cfg2_4x4": cfg2,
             "base_bs4": dict(base, sample=f"BASELINE configs[0]: BASE bs=4 {size}x{size}, 1 domain, fwd + BCE/Dice + bwd, "
                                           f"{base['warmup']} warm-up + {base['timed']} timed steps, median")}
+
+
+DUMP_PARAM_SAMPLE = 1 << 23          # 32 MB of float32 parameter values at most
+
+
+def dump_outputs(out_dir: str, result: dict, model) -> dict:
+    """--dump-outputs: what the last timed step hands its caller -- the returned loss tensors and the model it updated -- as
+    out_dir/<name>.npy (float32).  The parameters (35 M for MDViT, 140 MB) are sampled at DUMP_PARAM_SAMPLE positions of their
+    concatenation in named_parameters() order, drawn from a fixed seed: two runs of the same command dump the same positions."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in result.items() if torch.is_tensor(v) and v.is_floating_point()}
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            idx = torch.randint(flat.numel(), (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            arrays["params_sample"] = flat[idx.to(flat.device)].cpu().numpy()
+        else:
+            arrays["params"] = flat.cpu().numpy()
+        bufs = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+        if bufs:
+            arrays["buffers"] = torch.cat(bufs).cpu().numpy()
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def _free_port() -> int:
@@ -338,7 +377,7 @@ def main():
     fuse = max(1, min(len(domains), args.fuse_images // max(1, args.batch))) if args.model in ("mdvit", "mdvit_dsn") else 1
 
     drift = None
-    if args.precision == "bf16" and args.model == "mdvit":
+    if args.full and args.precision == "bf16" and args.model == "mdvit":
         # what the speed mode costs in accuracy: the same weights and images through the parity arithmetic and through bf16
         import torch.nn.functional as F
         img0 = pool[0][0][0][:2]
@@ -406,7 +445,7 @@ def main():
     # on a box 395 images/s, the second 433, the third and later 435-438).  The settle loop repeats untimed steps, five at a time, until the host's enqueue
     # time sits comfortably under the step time (the GPU is the limit again), for at most --settle-seconds; what it did is reported in the JSON (`settle`).
     settle = {"steps": 0, "seconds": 0.0, "host_ms_first": None, "host_ms_last": None}
-    if args.settle_seconds > 0 and not args.graph and world == 1 and args.model in ("mdvit", "mdvit_dsn") and args.decoder != "Transformer":
+    if args.full and not args.dump_outputs and args.settle_seconds > 0 and not args.graph and world == 1 and args.model in ("mdvit", "mdvit_dsn") and args.decoder != "Transformer":
         # (the configurations whose step is GPU-bound on a warm box; TransFuse / BASE / the Transformer peers are host-bound by nature and would only burn the budget)
         ts0 = time.perf_counter()
         hist = []
@@ -430,7 +469,7 @@ def main():
                 break
         settle.update(seconds=round(time.perf_counter() - ts0, 1), host_ms_first=round(hist[0], 1), host_ms_last=round(hist[-1], 1))
         waited[0] = 0.0
-    use_events = not args.no_kernel_events and not args.graph
+    use_events = args.full and not args.no_kernel_events and not args.graph
     # Round 6: the roofline kernel is found and timed by the LIBRARY's launch sampler (mdvit_gemm_sampler): kernel begin / end timestamps around the launches mdvit_gemm_f32
     # issues wherever it is called from -- the C-level block entry's products on the weight-gradient stream included, which the Python wrapper's event sampler never saw
     # (the largest kernel of the traced step was not a candidate).  --by-shape / --detail keep the wrapper's per-shape table.
@@ -480,6 +519,9 @@ def main():
         table = {k: v for k, v in sampler_read().items() if v["n"] > 0}
     else:
         table = ops.kernel_events_end() if use_events else {}
+    dumped = None
+    if args.dump_outputs and rank == 0:          # before any untimed step below moves the weights again
+        dumped = dump_outputs(args.dump_outputs, last, model)
     # one more, untimed step under the library's GEMM launch ledger: EVERY mdvit_gemm_f32 call of a step by kernel symbol -- the C-level block entry's included, which the
     # event sampler above never sees -- so that the roofline line's launch count / bytes per launch and the committed rocprofv3 average describe one launch population
     ledger = {}
@@ -499,7 +541,7 @@ def main():
                 if led_k and led_k["launches"]:
                     v["flop"], v["bytes"] = led_k["flop"] / led_k["launches"] * v["n"], led_k["bytes"] / led_k["launches"] * v["n"]
         shapes_out = os.environ.get("MDVIT_BENCH_GEMM_SHAPES")
-        if shapes_out:          # measurement aid: one more untimed step with the ledger keyed by (kernel, shape, epilogue operands) -> a text table
+        if shapes_out:          # measurement aid (--full): one more untimed step with the ledger keyed by (kernel, shape, epilogue operands) -> a text table
             # EVERY rank runs the extra step (it issues the bucket all-reduces and fence() holds a barrier: ADVICE r05); rank 0 writes the file
             _L.call("mdvit_gemm_ledger", 2)
             step(args.warmup + args.steps + 1)
@@ -534,7 +576,7 @@ def main():
     # fwd / bwd / optimizer split (the metric's "fwd+bwd ms"): two extra, untimed, instrumented steps -- each phase ends with an
     # event on the main stream (the backward's events come after the side stream has been joined)
     phase_ms = None
-    if args.model in ("mdvit", "mdvit_dsn") and not args.graph:
+    if args.full and args.model in ("mdvit", "mdvit_dsn") and not args.graph:
         acc_ms = {"fwd": 0.0, "bwd": 0.0, "opt": 0.0}
         reps = 2
         for i in range(reps):
@@ -599,13 +641,13 @@ def main():
                 with open(args.detail, "w") as f:
                     json.dump({"step_ms": dt * 1e3 / args.steps, "kernels": table}, f, indent=1)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 cpu = cpu_baseline(args.size)
             except Exception as e:           # the baseline is a report, never a reason to lose the GPU number
                 cpu = {"error": repr(e)}
         extra = {}
-        if world == 1 and not args.no_extra_legs and args.model == "mdvit" and args.batch != 32 and args.size == 512 and not args.host_inputs:
+        if args.full and world == 1 and not args.no_extra_legs and args.model == "mdvit" and args.batch != 32 and args.size == 512 and not args.host_inputs:
             # the metric is quoted "at bs=4/32" and the target on the MHSA+DA block at bs=32: run both as CHILD processes once
             # this process has handed its HBM back (a 128-image forward keeps ~115 GB of activations)
             del model, accum, opt, pool, last
@@ -613,7 +655,7 @@ def main():
             import gc
             gc.collect()
             torch.cuda.empty_cache()
-            common = ["--precision", args.precision] + (["--no-side-stream"] if args.no_side_stream else [])
+            common = ["--full", "--precision", args.precision] + (["--no-side-stream"] if args.no_side_stream else [])
             b32 = _child_json([sys.executable, os.path.abspath(__file__), "--batch", "32", "--steps", "8", "--warmup", "3", "--no-cpu-baseline",
                                "--no-extra-legs", "--no-kernel-events"] + common, 600)
             extra["bs32"] = {k: b32.get(k) for k in ("value", "unit", "ms_per_step", "phase_ms", "steps", "warmup", "memory", "host_enqueue_ms_per_step", "error") if k in b32}
@@ -622,7 +664,7 @@ def main():
             if args.precision == "bf16x3":
                 # the bf16 speed mode NEXT TO the parity-mode headline (never instead of it)
                 sp = _child_json([sys.executable, os.path.abspath(__file__), "--precision", "bf16", "--steps", str(args.steps), "--warmup", str(args.warmup),
-                                  "--no-cpu-baseline", "--no-extra-legs", "--no-kernel-events"] + (["--no-side-stream"] if args.no_side_stream else []), 600)
+                                  "--full", "--no-cpu-baseline", "--no-extra-legs", "--no-kernel-events"] + (["--no-side-stream"] if args.no_side_stream else []), 600)
                 extra["bf16_speed_mode"] = {k: sp.get(k) for k in ("value", "unit", "ms_per_step", "dtype", "drift_vs_parity_mode", "error") if k in sp}
             # BASELINE configs[0] (BASE, 1 domain x bs=4, 512x512: the case cpu_baseline.base_bs4 times on the host) on the GPU
             # (4 images per step: the eager step is host-bound at ~17 ms, so this leg replays the captured HIP graph of the step)
@@ -633,7 +675,7 @@ def main():
             if "config" in bb:
                 extra["base_bs4_gpu"]["workload"] = bb["config"]["workload"]
             # BASELINE configs[3]: bs=16 per domain, bf16 GEMMs / fp32 losses (one 64-image fused forward)
-            b16 = _child_json([sys.executable, os.path.abspath(__file__), "--batch", "16", "--precision", "bf16", "--steps", "5", "--warmup", "3", "--no-cpu-baseline",
+            b16 = _child_json([sys.executable, os.path.abspath(__file__), "--batch", "16", "--precision", "bf16", "--steps", "5", "--warmup", "3", "--full", "--no-cpu-baseline",
                                "--no-extra-legs", "--no-kernel-events"] + (["--no-side-stream"] if args.no_side_stream else []), 600)
             extra["bs16_bf16"] = {k: b16.get(k) for k in ("value", "unit", "ms_per_step", "dtype", "phase_ms", "drift_vs_parity_mode", "memory", "error") if k in b16}
             if "config" in b16:
@@ -711,6 +753,8 @@ def main():
             "memory": {"peak_allocated_gib": round(torch.cuda.max_memory_allocated() / 2**30, 2), "peak_reserved_gib": round(torch.cuda.max_memory_reserved() / 2**30, 2),
                        "device_mallocs": int(torch.cuda.memory_stats().get("num_device_alloc", 0)), "alloc_retries": int(torch.cuda.memory_stats().get("num_alloc_retries", 0))},
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         line.update(extra)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -355,6 +355,19 @@ def gen_transfuse_step(ns_unused=None, S=256, B=2, seed=12):
         out["grad__" + n] = dict(m.named_parameters())[n].grad.reshape(-1)[::7].numpy().copy()
     for k in ("resnet.bn1.running_mean", "up_c.residual.bn1.running_var", "up_c_2_2.attn_block.psi.1.running_mean"):
         out["buf__" + k] = m.state_dict()[k].numpy().copy()
+    # the same step in fp64: a few fp32 gradients (BatchNorm weights / attention gates whose ~1e5 terms cancel to ~1e-4) move by percents
+    # with the summation order of the CPU's kernels; in fp64 every gradient norm is fixed to ~1e-12, whatever machine runs the check
+    m = tf.TransFuse_S_adapt(num_classes=1, drop_rate=0.0, normal_init=False, pretrained=False, num_domains=4)
+    load_params_into(m, pn)
+    m.double().train()
+    tot = 0.0
+    for d in (1, 3):
+        img, lab = synth_image(1200 + d, B, S, S).double(), synth_label(1300 + d, B, S, S).double()
+        m4, m3, m2 = m(img, F.one_hot(torch.full((B,), d, dtype=torch.long), 4).double())
+        tot = tot + 0.5 * structure_loss(m2, lab) + 0.3 * structure_loss(m3, lab) + 0.2 * structure_loss(m4, lab)
+    tot.backward()
+    names64, out["grad_norms_f64"], _ = grad_digest({n: p.grad for n, p in m.named_parameters()})
+    assert names64 == names
     return out
 
 

@@ -278,8 +278,21 @@ def test_transfuse_oracle_vs_golden(golden):
         assert abs(l - float(g[f"loss_{d}"])) <= 2e-4 * abs(float(g[f"loss_{d}"]))
     names, norms, heads = grad_digest(grads)
     assert list(names) == [str(n) for n in g["grad_names"]]
-    ref = g["grad_norms"]
-    rel = np.abs(norms - ref) / np.maximum(ref, 1e-6 * ref.max())
+    # 52 of the 414 fp32 gradients (BatchNorm weights / attention gates whose ~1e5 terms cancel to ~1e-4, biases in front of a BatchNorm)
+    # are round-off: their norm moves by up to 5 % with the summation order of the CPU's kernels (the reference's own fp32 against its fp64
+    # step), so in fp32 they agree only on the machine that wrote the fixture.  fp32: every gradient that is not round-off within 5e-3;
+    # fp64: every gradient against the reference's fp64 step within 1e-8
+    ref, ref64 = g["grad_norms"], g["grad_norms_f64"]
+    floor = 1e-6 * ref64.max()
+    settled = np.abs(ref - ref64) / np.maximum(ref64, floor) < 1e-3
+    assert settled.sum() >= 360, int(settled.sum())
+    rel = np.where(settled, np.abs(norms - ref) / np.maximum(ref, 1e-6 * ref.max()), 0.0)
     assert rel.max() < 5e-3, (names[int(rel.argmax())], float(rel.max()))
+    P64 = {k: (v.double() if v.is_floating_point() else v) for k, v in T.to_torch(pn).items()}
+    _, grads64 = T.transfuse_train_step(P64, [(img.double(), lab.double(), d) for img, lab, d in batches], T.TFState(training=True))
+    names64, norms64, _ = grad_digest(grads64)
+    assert names64 == names
+    rel64 = np.abs(norms64 - ref64) / np.maximum(ref64, floor)
+    assert rel64.max() < 1e-8, (names[int(rel64.argmax())], float(rel64.max()))
     for k in ("resnet.bn1.running_mean", "up_c.residual.bn1.running_var", "up_c_2_2.attn_block.psi.1.running_mean"):
         assert np.abs(P[k].numpy() - g["buf__" + k]).max() <= 2e-4 * max(np.abs(g["buf__" + k]).max(), 1e-6), k

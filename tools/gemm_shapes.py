@@ -1,4 +1,4 @@
-"""Print the per-shape GEMM table of a `bench.py --by-shape --detail out.json` run (ms/step, TFLOP/s, GB/s)."""
+"""Print the per-shape GEMM table of a `bench.py --full --by-shape --detail out.json` run (ms/step, TFLOP/s, GB/s)."""
 import json, sys
 d = json.load(open(sys.argv[1]))
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 1

@@ -1,5 +1,5 @@
 """Every product of one bench step, timed ALONE on the GPU in the planner's own configuration and priced against its roofline:
-    MDVIT_BENCH_GEMM_SHAPES=shapes.txt python bench.py --steps 3 --warmup 2 --no-extra-legs --no-cpu-baseline      (writes the step's product list: the library's launch ledger, mode 2)
+    MDVIT_BENCH_GEMM_SHAPES=shapes.txt python bench.py --full --steps 3 --warmup 2 --no-extra-legs --no-cpu-baseline      (writes the step's product list: the library's launch ledger, mode 2)
     python tools/gemm_shapes_time.py shapes.txt [kernel-name filter]
 Per row: launches per step, us alone, GB/s and TF/s, the larger of (bytes / 8 TB/s, flop / bf16x3 roof) over the measured time.  The last line weighs the rows by launches per step --
 the isolated counterpart of bench.py's `roofline.frac` (which is measured inside the three-stream step).  The implicit 3x3 convolutions are listed but not timed here."""

@@ -1,5 +1,5 @@
 """Ground truth for the GEMM planner: time every (tile config, K-split) of the shapes a bench step uses and compare
-with the planner's pick.  usage: python tools/gemm_sweep.py shapes.json [top]   (shapes.json from bench.py --by-shape --detail)"""
+with the planner's pick.  usage: python tools/gemm_sweep.py shapes.json [top]   (shapes.json from bench.py --full --by-shape --detail)"""
 import ctypes as C, json, re, sys
 import torch
 from mdvit_amd import _lib, ops

@@ -10,19 +10,19 @@ REPO=$PWD
 OUT=$REPO/gpurun_out
 mkdir -p "$OUT"
 export PYTHONPATH=$REPO
-python3 bench.py > "$OUT/${TAG}_bench_bs4.json" 2> "$OUT/${TAG}_bench.err"
+python3 bench.py --full > "$OUT/${TAG}_bench_bs4.json" 2> "$OUT/${TAG}_bench.err"
 python3 tools/block_roofline.py --batch 32 --json "$OUT/${TAG}_block_roofline_bs32.json" > "$OUT/${TAG}_block_roofline_bs32.txt" 2> /dev/null
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_trace" -o bench -- python3 "$REPO/bench.py" --steps 3 --warmup 1 --no-cpu-baseline \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_trace" -o bench -- python3 "$REPO/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline \
     > "$OUT/${TAG}_bench_bs4_under_rocprof.json" 2> "$OUT/${TAG}_trace.err"
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/${TAG}_pmc_fetch" -o pmc -- python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events \
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/${TAG}_pmc_fetch" -o pmc -- python3 "$REPO/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events \
     > "$OUT/${TAG}_pmc_fetch.log" 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/${TAG}_pmc_write" -o pmc -- python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events \
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/${TAG}_pmc_write" -o pmc -- python3 "$REPO/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events \
     > "$OUT/${TAG}_pmc_write.log" 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_tf_trace" -o bench -- python3 "$REPO/bench.py" --model transfuse --batch 8 --size 256 --steps 3 --warmup 1 \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_tf_trace" -o bench -- python3 "$REPO/bench.py" --full --model transfuse --batch 8 --size 256 --steps 3 --warmup 1 \
     --no-cpu-baseline --no-kernel-events > "$OUT/${TAG}_transfuse_bs8_under_rocprof.json" 2> "$OUT/${TAG}_tf_trace.err"
 cd "$REPO"
-python3 bench.py --model transfuse --batch 8 --size 256 --no-cpu-baseline > "$OUT/${TAG}_transfuse_bs8.json" 2>> "$OUT/${TAG}_bench.err"
+python3 bench.py --full --model transfuse --batch 8 --size 256 --no-cpu-baseline > "$OUT/${TAG}_transfuse_bs8.json" 2>> "$OUT/${TAG}_bench.err"
 TF=$(ls "$OUT/${TAG}_tf_trace"/*kernel_stats.csv 2>/dev/null | head -1)
 [ -n "$TF" ] && cp "$TF" "$OUT/${TAG}_transfuse_bs8_kernel_stats.csv"
 rm -rf "$OUT/${TAG}_tf_trace"
