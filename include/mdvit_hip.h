@@ -341,9 +341,6 @@ int mdvit_mlp_rc_planes(int32_t planes);
 /* tuning hook: whether mdvit_block_bwd runs the C = 64 MLP backward as ONE kernel (mdvit_mlp_rc_bwd) -- 0 never, 1 always (default), 2 only when the call has no
  * weight-gradient stream (with one, the separate weight-gradient kernel overlaps the main stream's chain; measured, the one kernel still wins or ties).  Set it before mdvit_block_bwd_ws_bytes: the workspace layout follows it. */
 int mdvit_block_config(int32_t mlp_bwd_fused);
-/* tuning hook (tools/attn_time.py --apply-mode): how the attention backward's apply kernel (Ch = 8 / 16) orders its loads -- 0: each 32-token tile's rows in front of
- * the tile (default), 1: the MFMA operand rows one tile ahead at two waves per SIMD, 2: the same at one wave per SIMD.  Same arithmetic in every mode. */
-int mdvit_factoratt_config(int32_t apply_mode, int32_t apply_tiles /* 32-token tiles per workgroup of the apply kernels; 0: the launcher's rule */);
 int mdvit_mlp_rc_wgrad(const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, float* dW1, float* db1, float* dW2,
                        void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t hidden, float drop_p, uint32_t key1_0, uint32_t key1_1,
                        const uint32_t* drop_seed, int32_t accumulate, void* stream);
@@ -575,7 +572,9 @@ int mdvit_da_bwd(const float* label, const float* W1, const float* b1, const flo
  * with M = softmax_over_tokens(k)^T v.  crpe weights: [s3*Ch,1,3,3], [s5*Ch,1,5,5], [s7*Ch,1,7,7] (+bias).
  * a == NULL: no domain adapter (mpvit.py:347-373).  kmax/ksum [B,C] and Mmat [B,C,Ch] are saved for backward.
  * Backward returns dqkv, the crpe gradients (all six may be NULL: dgrad only) and e = a * dL/da (NULL when a is NULL).  dqkv == NULL: e alone (one pass over dout and out) --
- * what the data-gradient-only sweep needs at the first adapter of the network. */
+ * what the data-gradient-only sweep needs at the first adapter of the network.
+ * Built (C, heads): (64, 8) and (128, 8) -- head dim 8 / 16 -- and head dim 40 / 64 with C <= 512 (MDViT: (320, 8), (512, 8)); mdvit_factoratt_fwd / _bwd answer
+ * MDVIT_E_SHAPE for anything else, before any launch. */
 size_t mdvit_factoratt_ws_bytes(int32_t B, int32_t N, int32_t C, int32_t heads);
 int mdvit_factoratt_fwd(const float* qkv, const float* w3, const float* b3, const float* w5, const float* b5,
                         const float* w7, const float* b7, const float* a, float* out, float* U, float* kmax, float* ksum, float* Mmat,

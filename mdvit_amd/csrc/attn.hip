@@ -3,14 +3,14 @@
 // forward and backward.  There is no N x N score matrix: softmax runs over the
 // TOKEN axis of K per (batch, channel) column, M = softmax(K)^T V is Ch x Ch per head.
 //
-//   fwd  A: per (token tile, channel group, batch): tile column max / exp-sum / partial K^T V on fp32 MFMA  -> ws
+//   fwd  A: per (token tile, channel group, batch): tile column max / exp-sum / partial K^T V (fp32 MFMA at Ch = 40 / 64, a VALU stream at Ch = 8 / 16)  -> ws
 //        B: combine tiles (rescale by exp(m_t - m)) -> M [B,C,Ch], column stats kmax/ksum [B,C]
 //        C: U = dwconv_{3|5|7}(v) + bias (LDS-tiled, conv_tile.h; saved);  out = a * (Ch^-0.5 * q.M + q * U)
 //   bwd  1: dU = a*G*q (stored), e[b,c] = sum_n G*out as per-workgroup partial rows + fixed-order reduce
 //        2: dM = Q^T dFA via the same MFMA tile partials, summed by the batched partial reducer
 //        3: crpe weight/bias gradients (tile kernel + finish kernel per window size; mdvit_factoratt_wgrad lets the
 //           caller run them on a side stream), conv^T(dU) with the flipped windows
-//        4: dq, dk, dv on fp32 MFMA per channel group (t = sum_e dM*M folded into its staging)
+//        4: dq, dk, dv per channel group, MFMA or VALU stream by head width as in A (t = sum_e dM*M folded into its staging)
 // HBM-bound kernels: lanes run along channels (coalesced float4), the Ch x Ch products sit on the matrix cores, token-axis
 // reductions are two-stage (partials in a workspace, then a fixed-order combine): deterministic, hundreds of workgroups.
 #include "common.h"
@@ -19,11 +19,6 @@
 namespace {
 
 constexpr int FA_T = 64;      // tokens per tile in the partial (K^T V / Q^T dFA) kernels
-
-// the value of lane ^ 1 (a DPP quad permute [1, 0, 3, 2]: no LDS crossbar, no address register -- __shfl_xor compiles to ds_bpermute_b32)
-__device__ __forceinline__ float fa_dpp_xor1(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-}
 
 struct FaGeom {
     int B, H, W, N, C, heads, Ch, s3, s5, s7;
@@ -36,7 +31,8 @@ struct FaGeom {
 // One workgroup = FA_T tokens x one channel group of GW = max(Ch, 32) channels.  Both operand tiles are staged in LDS
 // (float4 loads, all in flight before the first LDS store); the GW x GW product X^T Y runs on v_mfma_f32_32x32x2_f32
 // with the token axis as k -- each wavefront takes a quarter of the tokens, the four partial results meet in LDS in a
-// fixed order -- and only the head-diagonal Ch x Ch blocks are written out.
+// fixed order -- and only the head-diagonal Ch x Ch blocks are written out.  Instantiated for Ch = 40 / 64 (one head per group); Ch = 8 / 16 run the streaming
+// form below (fa_partial_s8_kernel).
 typedef float fap_f32x16 __attribute__((ext_vector_type(16)));
 
 // Round 4: a workgroup walks NSUB consecutive 64-token tiles and keeps ONE partial result for all of them (online softmax across its tiles: running column
@@ -231,7 +227,10 @@ __global__ __launch_bounds__(256) void fa_partial_kernel(const float* __restrict
     }
 }
 
-// ---- the same tile partials at Ch = 8 / 16 (C = 64 / 128) as a STREAM (round 6; see fa_bwd_apply_s8_kernel for the layout) ------------------------------
+// ---- the same tile partials at Ch = 8 / 16 (C = 64 / 128) as a STREAM (round 6) ---------------------------------------------------------------------------
+// At these head widths the Ch x Ch products are a few fused multiply-adds per element: cheap enough for the VALU, where 32 x 32 MFMA tiles of block-diagonal matrices are
+// 15/16 (Ch = 8) or 3/4 (Ch = 16) zeros and their operand quads touch 32 cache lines per wave-wide load.  So the layout is chosen for the MEMORY system (it is also the
+// layout of fa_bwd_apply_tab_kernel): every load / store instruction moves whole contiguous token rows.
 // C / 4 lanes x float4 cover one token's channels (16 lanes at C = 64: four tokens per wave; 32 at C = 128: two); a lane owns four channels c and keeps P[c][.] (its
 // head's Ch columns, local order [mine | lane ^ 1's | lane ^ 2's | lane ^ 3's]) in 4 Ch registers for its whole token run; the other lanes' parts of the head's Y vector
 // come by DPP quad permutes (a head is 2 or 4 neighbouring lanes: always inside a quad).  No LDS staging, no MFMA (Ch multiply-adds per element of X), whole rows per load
@@ -514,286 +513,18 @@ __global__ __launch_bounds__(256) void fa_bwd_prep_kernel(const float* __restric
 }
 
 // ---- bwd 5: dq, dk, dv ----------------------------------------------------------------------------
-// Per image and head three token x Ch x Ch products (dq = dFA.KV^T, dP = v.dKV^T, dv = P.dKV) plus element-wise terms.
-// They run on v_mfma_f32_32x32x2_f32 as D[channel][token] = W[channel][k] . X[k][token]:
-//   * a wavefront owns 32 tokens of one channel GROUP (GW = max(Ch, 32) channels = 4/2/1/1 heads for Ch = 8/16/40/64);
-//     for Ch < 32 the small matrices are staged block-diagonally in LDS so one 32-wide MFMA tile serves several heads;
-//   * lane (token = lane % 32, half = lane / 32) holds its token's channels as the quads {32*(q/4) + 8*(q%4) + 4*half},
-//     and the k index of MFMA step kk is mapped to exactly those channels -- so the values a lane loads (float4, once)
-//     are both its MFMA operands and the element-wise terms of the 4-consecutive-channel quads the MFMA hands back to it;
-//   * W elements come from LDS (row stride GW + 1: conflict-free for row- and column-wise walks).
-// The kernel is HBM-bound: reads dout, k, v, U, dVc, writes dq|dk|dv, each exactly once.
-typedef float fa_f32x16 __attribute__((ext_vector_type(16)));
-
-// MODE (round 5, A/B by mdvit_factoratt_config): 0 = a tile's rows requested right in front of it (round 4's order, U / dVc moved to the top of the tile);
-// 1 = the MFMA operand rows one tile ahead, two waves per SIMD; 2 = the same at ONE wave per SIMD (512 registers: nothing spills)
-template <int CH, int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CH <= 16 && MODE != 2) ? 2 : 1, (CH <= 16 && MODE != 2) ? 2 : 1))) void fa_bwd_apply_kernel(const float* __restrict__ dout, const float* __restrict__ qkv,
-                                                           const float* __restrict__ U, const float* __restrict__ dVc,
-                                                           const float* __restrict__ Mmat, const float* __restrict__ a,
-                                                           const float* __restrict__ kmax, const float* __restrict__ ksum,
-                                                           const float* __restrict__ dMp, int NTS,
-                                                           float* __restrict__ dqkv, FaGeom g, int tiles_per_block) {
-    // dMp: the NTS partial rows [B][NTS][C][CH] of dM = Q^T dFA straight from fa_partial_kernel -- summed here in a fixed order while the block-diagonal
-    // matrices are staged (round 4: the separate reduction launch per block and sweep is gone; each workgroup re-adds GW x CH x NTS floats, a few KB)
-    constexpr int GW = CH < 32 ? 32 : CH;          // channels per group
-    constexpr int NB = (GW + 31) / 32;             // 32-channel MFMA row blocks
-    constexpr int NQ = GW / 8;                     // float4 quads per lane
-    constexpr int KS = GW / 2;                     // MFMA k-steps
-    constexpr int LD = GW + 1;
-    __shared__ float sKV[GW * LD], sD[GW * LD];
-    __shared__ __attribute__((aligned(16))) float s_a[GW], s_km[GW], s_ks[GW], s_tc[GW];
-    const int C = g.C, C3 = 3 * C;
-    const int b = blockIdx.z, g0 = blockIdx.y * GW;
-    for (int i = threadIdx.x; i < GW * GW; i += 256) {
-        const int r = i / GW, cc = i % GW;
-        const bool same = (r / CH) == (cc / CH);
-        const long src = ((long)b * C + g0 + r) * CH + (cc % CH);
-        sKV[r * LD + cc] = same ? Mmat[src] : 0.f;
-        float dm = 0.f;
-        if (same) {                       // eight independent loads at a time (a chain of NTS dependent loads cost a workgroup ~30 us of start-up)
-            const float* pp = dMp + (((long)b * NTS) * C + g0 + r) * CH + (cc % CH);
-            const long rs = (long)C * CH;
-            for (int t0 = 0; t0 < NTS; t0 += 8) {
-                float v8[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { const int t = t0 + u; v8[u] = pp[(long)(t < NTS ? t : NTS - 1) * rs]; if (t >= NTS) v8[u] = 0.f; }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) dm += v8[u];
-            }
-        }
-        sD[r * LD + cc] = dm;
-    }
-    for (int i = threadIdx.x; i < GW; i += 256) {
-        const long ci = (long)b * C + g0 + i;
-        s_a[i] = a ? a[ci] : 1.f; s_km[i] = kmax[ci]; s_ks[i] = 1.0f / ksum[ci];
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < GW; i += 256) {
-        float tc = 0.f;                   // t[c] = sum_e dM[c][e] * M[c][e]  (= sum_n P[n,c] dP[n,c], the column-softmax correction)
-        const int h0 = (i / CH) * CH;
-        for (int e = 0; e < CH; ++e) tc = fmaf(sD[i * LD + h0 + e], sKV[i * LD + h0 + e], tc);
-        s_tc[i] = tc;
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = lane & 31, half = lane >> 5;
-    const int ntiles = (g.N + 31) / 32;
-    const int tile_beg = blockIdx.x * tiles_per_block, tile_end = min(ntiles, tile_beg + tiles_per_block);
-    const float inv_scale = 1.0f / g.scale;
-    // Round 5: software prefetch.  The MFMA operand rows of a tile (dout, k, v) are requested one tile AHEAD and its epilogue rows (U, conv^T(dU)) at the top of the tile,
-    // all unconditionally (clamped token): they fly under the ~3000 cycles of MFMAs in front of their use; before, every tile paid its own load round trip in front of its
-    // first MFMA and a second one (U, dVc -- loaded under `if (ok)`) behind its last: 2.4-2.9 TB/s.  Two register sets alternate (the loop body holds two tiles: no copies).
-    struct Rows { float4 g[NQ], k[NQ], v[NQ]; };
-    auto request = [&](Rows& r, int tile) __attribute__((always_inline)) {
-        const long tok = (long)b * g.N + min(tile * 32 + t, g.N - 1);
-        const float* grow = dout + tok * C + g0;
-        const float* krow = qkv + tok * C3 + C + g0;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int cq = 32 * (q / 4) + 8 * (q % 4) + 4 * half;
-            r.g[q] = *reinterpret_cast<const float4*>(grow + cq);
-            r.k[q] = *reinterpret_cast<const float4*>(krow + cq);
-            r.v[q] = *reinterpret_cast<const float4*>(krow + C + cq);
-        }
-    };
-    auto compute = [&](const Rows& r, int tile) __attribute__((always_inline)) {
-        const int n = tile * 32 + t;
-        const bool ok = n < g.N;
-        const long tok = (long)b * g.N + (ok ? n : g.N - 1);
-        float4 ru[NQ], rc[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int cq = 32 * (q / 4) + 8 * (q % 4) + 4 * half;
-            ru[q] = *reinterpret_cast<const float4*>(U + tok * C + g0 + cq);
-            rc[q] = *reinterpret_cast<const float4*>(dVc + tok * C + g0 + cq);
-        }
-        float dfa[NQ][4], vv[NQ][4], pp[NQ][4];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int cq = 32 * (q / 4) + 8 * (q % 4) + 4 * half;
-            const float4 g4 = r.g[q], k4 = r.k[q], v4 = r.v[q];
-            const float4 a4 = *reinterpret_cast<const float4*>(s_a + cq);
-            const float4 m4 = *reinterpret_cast<const float4*>(s_km + cq);
-            const float4 i4 = *reinterpret_cast<const float4*>(s_ks + cq);
-            const float z = ok ? 1.f : 0.f;          // out-of-range tokens contribute zeros (their results are not stored)
-            dfa[q][0] = z * g.scale * a4.x * g4.x; dfa[q][1] = z * g.scale * a4.y * g4.y;
-            dfa[q][2] = z * g.scale * a4.z * g4.z; dfa[q][3] = z * g.scale * a4.w * g4.w;
-            vv[q][0] = z * v4.x; vv[q][1] = z * v4.y; vv[q][2] = z * v4.z; vv[q][3] = z * v4.w;
-            pp[q][0] = z * expf(k4.x - m4.x) * i4.x; pp[q][1] = z * expf(k4.y - m4.y) * i4.y;
-            pp[q][2] = z * expf(k4.z - m4.z) * i4.z; pp[q][3] = z * expf(k4.w - m4.w) * i4.w;
-        }
-        fa_f32x16 acc1[NB], acc2[NB], acc3[NB];
-#pragma unroll
-        for (int ob = 0; ob < NB; ++ob)
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) { acc1[ob][rr] = 0.f; acc2[ob][rr] = 0.f; acc3[ob][rr] = 0.f; }
-#pragma unroll
-        for (int ob = 0; ob < NB; ++ob) {
-            const int orow = 32 * ob + t;                       // W row (output channel) this lane feeds
-            const bool rok = orow < GW;
-            const int orc = rok ? orow : 0;
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                const int q = kk / 4, j = kk % 4;
-                const int kc = 32 * (q / 4) + 8 * (q % 4) + 4 * half + j;      // channel of this lane's k slot
-                float w1 = sKV[orc * LD + kc], w2 = sD[orc * LD + kc], w3 = sD[kc * LD + orc];
-                if (!rok) { w1 = 0.f; w2 = 0.f; w3 = 0.f; }
-                acc1[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(w1, dfa[q][j], acc1[ob], 0, 0, 0);
-                acc2[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2, vv[q][j], acc2[ob], 0, 0, 0);
-                acc3[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(w3, pp[q][j], acc3[ob], 0, 0, 0);
-            }
-        }
-        if (ok) {
-            float* drow = dqkv + tok * C3 + g0;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int ob = q / 4, r0 = 4 * (q % 4);
-                const int cq = 32 * (q / 4) + 8 * (q % 4) + 4 * half;
-                const float4 u4 = ru[q], c4 = rc[q];
-                const float4 t4 = *reinterpret_cast<const float4*>(s_tc + cq);
-                float4 dq, dk, dv;
-                dq.x = fmaf(dfa[q][0] * inv_scale, u4.x, acc1[ob][r0 + 0]); dq.y = fmaf(dfa[q][1] * inv_scale, u4.y, acc1[ob][r0 + 1]);
-                dq.z = fmaf(dfa[q][2] * inv_scale, u4.z, acc1[ob][r0 + 2]); dq.w = fmaf(dfa[q][3] * inv_scale, u4.w, acc1[ob][r0 + 3]);
-                dk.x = pp[q][0] * (acc2[ob][r0 + 0] - t4.x); dk.y = pp[q][1] * (acc2[ob][r0 + 1] - t4.y);
-                dk.z = pp[q][2] * (acc2[ob][r0 + 2] - t4.z); dk.w = pp[q][3] * (acc2[ob][r0 + 3] - t4.w);
-                dv.x = acc3[ob][r0 + 0] + c4.x; dv.y = acc3[ob][r0 + 1] + c4.y;
-                dv.z = acc3[ob][r0 + 2] + c4.z; dv.w = acc3[ob][r0 + 3] + c4.w;
-                *reinterpret_cast<float4*>(drow + cq) = dq;
-                *reinterpret_cast<float4*>(drow + C + cq) = dk;
-                *reinterpret_cast<float4*>(drow + 2 * C + cq) = dv;
-            }
-        }
-    };
-    Rows ra, rb;
-    int tile = tile_beg + wave;
-    if (MODE == 0) {
-        for (; tile < tile_end; tile += 4) { request(ra, tile); compute(ra, tile); }
-        return;
-    }
-    if (tile < tile_end) request(ra, tile);
-    for (; tile < tile_end; tile += 8) {
-        request(rb, min(tile + 4, ntiles - 1));
-        compute(ra, tile);
-        if (tile + 4 < tile_end) {
-            request(ra, min(tile + 8, ntiles - 1));
-            compute(rb, tile + 4);
-        }
-    }
-}
-
-// ---- bwd 5 at Ch = 8, C = 64 as a STREAM (round 6) --------------------------------------------------------------------------------------------
-// fa_bwd_apply_kernel<8> runs the three token x 8 x 8 products of every head on 32 x 32 fp32 MFMA tiles of block-diagonal matrices (15/16 of every tile is zero) with
-// operand quads of 32 bytes per token and load instruction -- 32 cache lines per wave-wide load -- and sits at 3.3-3.9 TB/s of its eight [tokens, C] streams.  At Ch = 8
-// the products are 24 fused multiply-adds per output element: cheap enough for the VALU (the arithmetic below prices out at ~6x the HBM rate), so here the layout is
-// chosen for the MEMORY system instead: 16 lanes x float4 cover one token's 64 channels (every load / store instruction moves whole 256-byte rows, four tokens per wave),
-// a lane keeps the matrix rows / columns of ITS four channels in registers for its whole token run (96 values: M[c][.], dM[c][.], dM[.][c]) and gets the other half of
-// its head's 8-vector from the neighbouring lane with three 4-value DPP exchanges per token.  The next token's five rows are requested before the current one is used.
-// Same products; the sums run in the head's local channel order instead of the MFMA's (fp32 round-off only: tests compare against fp64 at 1e-4).
-__global__ __launch_bounds__(256) void fa_bwd_apply_s8_kernel(const float* __restrict__ dout, const float* __restrict__ qkv,
-                                                              const float* __restrict__ U, const float* __restrict__ dVc,
-                                                              const float* __restrict__ Mmat, const float* __restrict__ a,
-                                                              const float* __restrict__ kmax, const float* __restrict__ ksum,
-                                                              const float* __restrict__ dMp, int NTS,
-                                                              float* __restrict__ dqkv, FaGeom g, int tokens_per_block) {
-    constexpr int C = 64, CH = 8, C3 = 192;
-    __shared__ float sM[C * CH], sD[C * CH];
-    __shared__ float s_tc[C];
-    const int b = blockIdx.y;
-    for (int i = threadIdx.x; i < C * CH; i += 256) {
-        sM[i] = Mmat[(long)b * C * CH + i];
-        float dm = 0.f;
-        const float* pp = dMp + ((long)b * NTS) * C * CH + i;
-        const long rs = (long)C * CH;
-        for (int t0 = 0; t0 < NTS; t0 += 8) {          // (the summation order of fa_bwd_apply_kernel: eight independent loads at a time)
-            float v8[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { const int t = t0 + u; v8[u] = pp[(long)(t < NTS ? t : NTS - 1) * rs]; if (t >= NTS) v8[u] = 0.f; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) dm += v8[u];
-        }
-        sD[i] = dm;
-    }
-    __syncthreads();
-    if (threadIdx.x < C) {
-        float tc = 0.f;
-#pragma unroll
-        for (int e = 0; e < CH; ++e) tc = fmaf(sD[threadIdx.x * CH + e], sM[threadIdx.x * CH + e], tc);
-        s_tc[threadIdx.x] = tc;
-    }
-    __syncthreads();
-    const int q = threadIdx.x & 15, slot = threadIdx.x >> 4;
-    const int c0 = 4 * q, hb = (q >> 1) * CH, j0 = 4 * (q & 1), jo = j0 ^ 4;          // my four channels; my head; my / my neighbour's offset inside the head
-    // local order of a head's 8-vector: [mine (4) | the neighbour lane's (4)]
-    float Mr[4][8], Dr[4][8], Dc[8][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int l = 0; l < 8; ++l) {
-            const int e = l < 4 ? j0 + l : jo + (l - 4);
-            Mr[j][l] = sM[(c0 + j) * CH + e];          // dq[c] = sum_e dfa[e] M[c][e]
-            Dr[j][l] = sD[(c0 + j) * CH + e];          // dk[c] = P[c] (sum_e v[e] dM[c][e] - t[c])
-            Dc[l][j] = sD[(hb + e) * CH + j0 + j];     // dv[e'] = sum_c P[c] dM[c][e'],  e' = my channel j, c = the head's channel e
-        }
-    const long ci = (long)b * C + c0;
-    const float4 a4 = a ? *reinterpret_cast<const float4*>(a + ci) : make_float4(1.f, 1.f, 1.f, 1.f);
-    const float4 km4 = *reinterpret_cast<const float4*>(kmax + ci);
-    float4 is4 = *reinterpret_cast<const float4*>(ksum + ci);
-    is4 = make_float4(1.0f / is4.x, 1.0f / is4.y, 1.0f / is4.z, 1.0f / is4.w);
-    const float4 tc4 = *reinterpret_cast<const float4*>(s_tc + c0);
-    const float inv_scale = 1.0f / g.scale;
-    const int n_beg = blockIdx.x * tokens_per_block, n_end = min(g.N, n_beg + tokens_per_block);
-    struct Rows { float4 g, k, v, u, c; };
-    auto request = [&](Rows& r, int n) __attribute__((always_inline)) {
-        const long tok = (long)b * g.N + min(n, g.N - 1);
-        r.g = *reinterpret_cast<const float4*>(dout + tok * C + c0);
-        r.k = *reinterpret_cast<const float4*>(qkv + tok * C3 + C + c0);
-        r.v = *reinterpret_cast<const float4*>(qkv + tok * C3 + 2 * C + c0);
-        r.u = *reinterpret_cast<const float4*>(U + tok * C + c0);
-        r.c = *reinterpret_cast<const float4*>(dVc + tok * C + c0);
-    };
-    auto compute = [&](const Rows& r, int n) __attribute__((always_inline)) {
-        float dfa[8], vv[8], pp[8];
-        dfa[0] = g.scale * a4.x * r.g.x; dfa[1] = g.scale * a4.y * r.g.y; dfa[2] = g.scale * a4.z * r.g.z; dfa[3] = g.scale * a4.w * r.g.w;
-        vv[0] = r.v.x; vv[1] = r.v.y; vv[2] = r.v.z; vv[3] = r.v.w;
-        pp[0] = expf(r.k.x - km4.x) * is4.x; pp[1] = expf(r.k.y - km4.y) * is4.y; pp[2] = expf(r.k.z - km4.z) * is4.z; pp[3] = expf(r.k.w - km4.w) * is4.w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { dfa[4 + j] = fa_dpp_xor1(dfa[j]); vv[4 + j] = fa_dpp_xor1(vv[j]); pp[4 + j] = fa_dpp_xor1(pp[j]); }
-        float dq[4], dk[4], dv[4];
-        const float uu[4] = {r.u.x, r.u.y, r.u.z, r.u.w}, cc[4] = {r.c.x, r.c.y, r.c.z, r.c.w}, tcv[4] = {tc4.x, tc4.y, tc4.z, tc4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-            for (int l = 0; l < 8; ++l) { s1 = fmaf(dfa[l], Mr[j][l], s1); s2 = fmaf(vv[l], Dr[j][l], s2); s3 = fmaf(pp[l], Dc[l][j], s3); }
-            dq[j] = fmaf(dfa[j] * inv_scale, uu[j], s1);
-            dk[j] = pp[j] * (s2 - tcv[j]);
-            dv[j] = s3 + cc[j];
-        }
-        if (n < n_end) {
-            float* drow = dqkv + ((long)b * g.N + n) * C3 + c0;
-            *reinterpret_cast<float4*>(drow) = make_float4(dq[0], dq[1], dq[2], dq[3]);
-            *reinterpret_cast<float4*>(drow + C) = make_float4(dk[0], dk[1], dk[2], dk[3]);
-            *reinterpret_cast<float4*>(drow + 2 * C) = make_float4(dv[0], dv[1], dv[2], dv[3]);
-        }
-    };
-    // (every lane of a 16-lane row group runs the same trip count: the DPP exchange partners are always alive)
-    Rows ra, rb;
-    int n = n_beg + slot;
-    request(ra, n);
-    for (; n < n_end; n += 32) {
-        request(rb, n + 16);
-        compute(ra, n);
-        request(ra, n + 32);
-        compute(rb, n + 16);
-    }
-}
-
-// ---- bwd 5 at Ch = 16, C = 128 as a stream (round 6) ---------------------------------------------------------------------------------------------
-// The layout of fa_bwd_apply_s8_kernel with 32 lanes x float4 per token (two tokens per wave) and a head on the four lanes of a quad.  A lane's matrix rows / columns are
-// 192 values here -- more than the register file leaves next to two token sets in flight -- so they live in an LDS table [48 float4 slots][32 lane classes]: a wave-wide
-// ds_read_b128 of one slot is 512 contiguous bytes (conflict-free; the second token's lanes read the same addresses: broadcast).  48 reads per token and lane price out at
-// ~2.6x the HBM rate of the kernel's eight streams; the three 16-vectors of the head come by quad-permute DPP.
+// Per image and head three token x Ch x Ch products (dq = dFA.KV^T, dP = v.dKV^T, dv = P.dKV) plus element-wise terms, HBM-bound: dout, k, v, U, conv^T(dU) are
+// read and dq | dk | dv written, [tokens, C] streams all.  Ch = 8 / 16 (C = 64 / 128): fa_bwd_apply_tab_kernel, on the VALU.  Ch = 40 / 64: fa_bwd_apply3_kernel, on MFMA.
+//
+// fa_bwd_apply_tab_kernel: the streaming layout of fa_partial_s8_kernel -- C / 4 lanes x float4 cover one token's channels (16 lanes at C = 64: four tokens per wave; 32 at
+// C = 128: two), so every load / store instruction moves whole contiguous rows; a head is the 2 or 4 neighbouring lanes of a quad, and a lane gets the rest of its head's
+// three Ch-vectors (dFA, v, P) by quad-permute DPP (no LDS crossbar, no address register -- __shfl_xor compiles to ds_bpermute_b32).  The matrix rows / columns of a lane's
+// four channels (M[c][.], dM[c][.], dM[.][c]: 96 values at Ch = 8, 192 at Ch = 16 -- more than the register file leaves next to two token sets in flight) live in an LDS
+// table [8 Ch / 4 + Ch float4 slots][C / 4 lane classes]: a wave-wide ds_read_b128 of one slot is contiguous (conflict-free; the other tokens' lanes of the wave read the
+// same addresses: broadcast).  At Ch = 16 the 48 reads per token and lane price out at ~2.6x the HBM rate of the kernel's eight streams; at Ch = 8 the table beat the same
+// values held in 96 registers (214.8 against 221.7 us at 32 images).  The next token's five rows are requested before the current one is used.  The sums run in the head's
+// local channel order [mine | lane ^ 1's | lane ^ 2's | lane ^ 3's] (fp32 round-off only: tests compare against fp64 at 1e-4).
+typedef float fa_f32x16 __attribute__((ext_vector_type(16)));          // (fa_apply3_tiles' accumulators)
 template <int CH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void fa_bwd_apply_tab_kernel(const float* __restrict__ dout, const float* __restrict__ qkv,
                                                                const float* __restrict__ U, const float* __restrict__ dVc,
@@ -811,7 +542,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         float dm = 0.f;
         const float* pp = dMp + ((long)b * NTS) * C * CH + i;
         const long rs = (long)C * CH;
-        for (int t0 = 0; t0 < NTS; t0 += 8) {          // (the summation order of fa_bwd_apply_kernel: eight independent loads at a time)
+        for (int t0 = 0; t0 < NTS; t0 += 8) {          // (dMp: the NTS partial rows [B][NTS][C][CH] of dM = Q^T dFA straight from the partial kernel, summed in a fixed order -- eight independent loads at a time: a chain of NTS dependent loads cost a workgroup ~30 us of start-up)
             float v8[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) { const int t = t0 + u; v8[u] = pp[(long)(t < NTS ? t : NTS - 1) * rs]; if (t >= NTS) v8[u] = 0.f; }
@@ -915,6 +646,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
+// The same three products at Ch = 40 / 64 on v_mfma_f32_32x32x2_f32, as D[channel][token] = W[channel][k] . X[k][token]:
+//   * a wavefront owns 32 tokens of one head (the channel group: GW = Ch channels);
+//   * lane (token = lane % 32, half = lane / 32) holds its token's channels as the quads {32*(q/4) + 8*(q%4) + 4*half},
+//     and the k index of MFMA step kk is mapped to exactly those channels -- so the values a lane loads (float4, once)
+//     are both its MFMA operands and the element-wise terms of the 4-consecutive-channel quads the MFMA hands back to it;
+//   * W elements come from LDS (row stride GW + 1: conflict-free for row- and column-wise walks).
 // role 0: dq = a*scale*G . KV^T (+ G*a*U);  1: dk = P * (v . dM^T - t);  2: dv = P . dM + conv^T(dU)      -- fa_bwd_apply3_kernel's wave roles
 template <int CH, int ROLE>
 __device__ __forceinline__ void fa_apply3_tiles(const float* __restrict__ dout, const float* __restrict__ qkv, const float* __restrict__ U, const float* __restrict__ dVc,
@@ -1027,10 +764,10 @@ __device__ __forceinline__ void fa_apply3_tiles(const float* __restrict__ dout, 
     }
 }
 
-// The same three products for Ch >= 32 (one head per channel group) with the PRODUCTS dealt to wavefronts: wave role 0 forms dq, 1 dk, 2 dv of a 32-token
-// tile -- each with one accumulator set and the two operands its product needs (~1/3 of the registers: three waves per SIMD instead of the one that the
-// all-in-one wave above gets at Ch = 40 / 64, where 396 / 512 registers left the loads of a tile nothing to hide behind: 1.9 TB/s).  k is read by two roles
-// (the second read hits the L2).  Per output element the same MFMA sequence as above: same bits.
+// The three products for Ch >= 32 (one head per channel group) with the PRODUCTS dealt to wavefronts: wave role 0 forms dq, 1 dk, 2 dv of a 32-token
+// tile -- each with one accumulator set and the two operands its product needs (~1/3 of the registers: three waves per SIMD instead of the one that a wave
+// forming all three products of its tile gets at Ch = 40 / 64, where 396 / 512 registers left the loads of a tile nothing to hide behind: 1.9 TB/s; that
+// form is removed, see docs/history.md).  k is read by two roles (the second read hits the L2).
 template <int CH>
 __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(CH >= 64 ? 2 : 3, CH >= 64 ? 2 : 3))) void fa_bwd_apply3_kernel(const float* __restrict__ dout, const float* __restrict__ qkv,
                                                            const float* __restrict__ U, const float* __restrict__ dVc,
@@ -1060,7 +797,7 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(CH >= 64 ? 
         float dm = 0.f;
         const float* pp = dMp + (((long)b * NTS) * C + g0 + r) * CH + cc;
         const long rs = (long)C * CH;
-        for (int t0 = 0; t0 < NTS; t0 += 8) {          // (the summation order of fa_bwd_apply_kernel)
+        for (int t0 = 0; t0 < NTS; t0 += 8) {          // (the summation order of fa_bwd_apply_tab_kernel: the partial rows of dM, eight independent loads at a time)
             float v8[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) { const int t = t0 + u; v8[u] = pp[(long)(t < NTS ? t : NTS - 1) * rs]; if (t >= NTS) v8[u] = 0.f; }
@@ -1308,11 +1045,13 @@ size_t fa_ws_floats(int B, int N, int C, int heads) {
 // 64-token tiles a workgroup of the partial kernels walks.  A function of the IMAGE's token count alone -- never of the batch: an image's arithmetic (which
 // tiles meet in which partial row, in which order) must not depend on how many images share the launch, or the domain-batched forward stops being the
 // per-domain forwards bit for bit (tests/test_gpu_model.py: test_bench_step_fused_forward_equals_per_domain_at_512).
-int fa_nsub(int NT, int /*groups*/, int /*B*/) {
-    static const int env = [] { const char* e = getenv("MDVIT_FA_NSUB"); return e ? atoi(e) : 0; }();          // (experiments only: a fixed number of tiles per workgroup)
-    if (env > 0) return env < NT ? env : NT;
-    return NT >= 128 ? 8 : (NT >= 64 ? 4 : (NT >= 16 ? 2 : 1));
-}
+int fa_nsub(int NT) { return NT >= 128 ? 8 : (NT >= 64 ? 4 : (NT >= 16 ? 2 : 1)); }
+
+// The (C, heads) combinations the kernels are built for: 8 heads at C = 64 / 128 (Ch = 8 / 16: the streaming kernels are compiled for C == 8 Ch), and one head per
+// channel group at Ch = 40 / 64 with C <= 512 (MDViT: 8 heads at C = 320 / 512).
+bool fa_built(const FaGeom& g) { return ((g.Ch == 8 || g.Ch == 16) && g.heads == 8) || ((g.Ch == 40 || g.Ch == 64) && g.C <= 512); }
+#define FA_CHECK_BUILT(fn, g) MDVIT_CHECK_ARG(fa_built(g), MDVIT_E_SHAPE, fn ": C=%d with %d heads (head dim %d) not built: built are 8 heads at C = 64 / 128 (head dim 8 / 16) " \
+                                              "and head dim 40 / 64 with C <= 512 (8 heads at C = 320 / 512)", (g).C, (g).heads, (g).Ch)
 
 int quad_grid(long work_quads, int QC, int max_blocks) {
     // smallest grid >= wanted with (grid*256) % QC == 0
@@ -1327,22 +1066,13 @@ int quad_grid(long work_quads, int QC, int max_blocks) {
 
 }  // namespace
 
-// fa_bwd_apply_kernel's MODE (tuning hook: mdvit_factoratt_config).  Measured at 32 images (tools/probe/attn_kernel_trace.sh, profiles/r05_attn_kernels_isolated.txt): Ch = 8 / 16
-// 269 / 145 us in mode 0, 460 / 240 us in mode 1 (60 registers spill), 386 / 213 us in mode 2 (4 waves per CU): a wave of these launches owns 2 tiles (the grid is kept >= 2048
-// workgroups), nothing to prefetch across; the row-ahead order pays in fa_bwd_apply3_kernel, whose waves walk 4 tiles (Ch = 64: 79 -> 43 us).
-int g_fa_apply_mode = 0;
-int g_fa_apply_tiles = 0;       // 32-token tiles per workgroup of the apply kernels (0: the launcher's rule)
-extern "C" int mdvit_factoratt_config(int32_t apply_mode, int32_t apply_tiles) {
-    if (apply_mode < 0 || apply_mode > 2 || apply_tiles < 0) return mdvit_set_error(MDVIT_E_SHAPE, "factoratt_config: apply_mode in 0..2, apply_tiles >= 0");
-    g_fa_apply_mode = apply_mode; g_fa_apply_tiles = apply_tiles;
-    return MDVIT_OK;
-}
-
 extern "C" size_t mdvit_factoratt_ws_bytes(int32_t B, int32_t N, int32_t C, int32_t heads) {
     if (B <= 0 || N <= 0 || C <= 0 || heads <= 0 || C % heads) return 0;
     return fa_ws_floats(B, N, C, heads) * sizeof(float);
 }
 
+/* Supported (C, heads): (64, 8), (128, 8) -- head dim 8 / 16, the streaming kernels -- and any head count with head dim 40 / 64 and C <= 512 (MDViT: (320, 8), (512, 8)).
+ * Anything else is MDVIT_E_SHAPE, answered before any launch. */
 extern "C" int mdvit_factoratt_fwd(const float* qkv, const float* w3, const float* b3, const float* w5, const float* b5,
                                    const float* w7, const float* b7, const float* a, float* out, float* U, float* kmax, float* ksum, float* Mmat,
                                    void* ws, size_t ws_bytes, int32_t B, int32_t H, int32_t W, int32_t C, int32_t heads,
@@ -1350,43 +1080,33 @@ extern "C" int mdvit_factoratt_fwd(const float* qkv, const float* w3, const floa
     hipStream_t s = (hipStream_t)stream;
     FaGeom g;
     MDVIT_CHECK_ARG(make_geom(g, B, H, W, C, heads, s3, s5, s7), MDVIT_E_SHAPE, "factoratt_fwd: bad geometry B=%d H=%d W=%d C=%d heads=%d splits=%d/%d/%d", B, H, W, C, heads, s3, s5, s7);
+    FA_CHECK_BUILT("factoratt_fwd", g);
     MDVIT_CHECK_ARG(ws_bytes >= fa_ws_floats(B, g.N, C, heads) * sizeof(float), MDVIT_E_WORKSPACE, "factoratt_fwd: workspace too small (%zu bytes)", ws_bytes);
-    const int NT0 = cdiv(g.N, FA_T);
-    const int NSUB = fa_nsub(NT0, C / (g.Ch < 32 ? 32 : g.Ch), B);
+    const int Ch = g.Ch, NT0 = cdiv(g.N, FA_T);
+    const int NSUB = fa_nsub(NT0);
     const int NT = cdiv(NT0, NSUB);                    // partial rows per image
     float* ws_m = (float*)ws;
     float* ws_s = ws_m + (long)B * NT * C;
     float* ws_P = ws_s + (long)B * NT * C;
-    {
-        const int GW = g.Ch < 32 ? 32 : g.Ch;
-        MDVIT_CHECK_ARG(C % GW == 0, MDVIT_E_SHAPE, "factoratt_fwd: C=%d is not a multiple of the %d-channel group", C, GW);
-#define FA_PART_LAUNCH(CHV) hipLaunchKernelGGL((fa_partial_kernel<CHV, true>), dim3(NT, C / GW, B), dim3(256), 0, s, \
+#define FA_PART_STREAM(CHV) fa_partial_stream_launch<CHV, true>(dim3(NT, 1, B), s, qkv + C, (long)3 * C, qkv + 2 * C, (long)3 * C, nullptr, 1.f, ws_m, ws_s, ws_P, g, NT0, NSUB, nullptr, nullptr, nullptr)
+#define FA_PART_TILES(CHV) hipLaunchKernelGGL((fa_partial_kernel<CHV, true>), dim3(NT, C / CHV, B), dim3(256), 0, s, \
                        qkv + C, (long)3 * C, qkv + 2 * C, (long)3 * C, (const float*)nullptr, 1.f, ws_m, ws_s, ws_P, g, NT0, NSUB)
-        static const bool s8_env = [] { const char* e = getenv("MDVIT_FA_PARTIAL_STREAM"); return !(e && e[0] == '0'); }();
-        static const bool s16_env = [] { const char* e = getenv("MDVIT_FA_PARTIAL_STREAM16"); return !(e && e[0] == '0'); }();
-        if (g.Ch == 8 && C == 64 && s8_env)          // the streaming form (MDVIT_FA_PARTIAL_STREAM=0: the LDS / MFMA tiles, A/B)
-            fa_partial_stream_launch<8, true>(dim3(NT, 1, B), s, qkv + C, (long)3 * C, qkv + 2 * C, (long)3 * C, nullptr, 1.f, ws_m, ws_s, ws_P, g, NT0, NSUB, nullptr, nullptr, nullptr);
-        else if (g.Ch == 16 && C == 128 && s8_env && s16_env)
-            fa_partial_stream_launch<16, true>(dim3(NT, 1, B), s, qkv + C, (long)3 * C, qkv + 2 * C, (long)3 * C, nullptr, 1.f, ws_m, ws_s, ws_P, g, NT0, NSUB, nullptr, nullptr, nullptr);
-        else
-        switch (g.Ch) {
-            case 8: FA_PART_LAUNCH(8); break;
-            case 16: FA_PART_LAUNCH(16); break;
-            case 40: FA_PART_LAUNCH(40); break;
-            case 64: FA_PART_LAUNCH(64); break;
-            default: return mdvit_set_error(MDVIT_E_SHAPE, "factoratt_fwd: head dim %d not built (8/16/40/64)", g.Ch);
-        }
-#undef FA_PART_LAUNCH
+    switch (Ch) {          // (fa_built: no other head dim gets here)
+        case 8: FA_PART_STREAM(8); break;
+        case 16: FA_PART_STREAM(16); break;
+        case 40: FA_PART_TILES(40); break;
+        case 64: FA_PART_TILES(64); break;
     }
+#undef FA_PART_STREAM
+#undef FA_PART_TILES
     if (NT > 8)
         hipLaunchKernelGGL((fa_combine_softmax_kernel<32>), dim3(cdiv((long)C * g.Ch, 8), B), dim3(256), 0, s, ws_m, ws_s, ws_P, kmax, ksum, Mmat, g, NT);
     else if (NT > 2)
         hipLaunchKernelGGL((fa_combine_softmax_kernel<4>), dim3(cdiv((long)C * g.Ch, 64), B), dim3(256), 0, s, ws_m, ws_s, ws_P, kmax, ksum, Mmat, g, NT);
     else
         hipLaunchKernelGGL((fa_combine_softmax_kernel<1>), dim3(cdiv((long)C * g.Ch, 256), B), dim3(256), 0, s, ws_m, ws_s, ws_P, kmax, ksum, Mmat, g, NT);
-    MDVIT_CHECK_ARG(C <= 512, MDVIT_E_SHAPE, "factoratt_fwd: C=%d > 512 not built", C);
     // U = dwconv_win(v) + bias, one tiled launch per window class (channels [0,s3*Ch) | [..) | [..))
-    const int Ch = g.Ch, c5 = s3 * Ch, c7 = (s3 + s5) * Ch;
+    const int c5 = s3 * Ch, c7 = (s3 + s5) * Ch;
     const CtGeom cg{B, g.H, g.W};
     {   // the three window classes in one launch
         const int xoff[3] = {2 * C, 2 * C + c5, 2 * C + c7}, yoff[3] = {0, c5, c7}, ncls[3] = {s3 * Ch, s5 * Ch, s7 * Ch};
@@ -1406,7 +1126,6 @@ extern "C" int mdvit_factoratt_fwd(const float* qkv, const float* w3, const floa
             case 16: FA_OUT_LAUNCH(16); break;
             case 40: FA_OUT_LAUNCH(40); break;
             case 64: FA_OUT_LAUNCH(64); break;
-            default: return mdvit_set_error(MDVIT_E_SHAPE, "factoratt_fwd: head dim %d not built (8/16/40/64)", Ch);
         }
 #undef FA_OUT_LAUNCH
     }
@@ -1414,6 +1133,7 @@ extern "C" int mdvit_factoratt_fwd(const float* qkv, const float* w3, const floa
     return MDVIT_OK;
 }
 
+/* Supported (C, heads): as mdvit_factoratt_fwd. */
 extern "C" int mdvit_factoratt_bwd(const float* dout, const float* qkv, const float* out, const float* U,
                                    const float* w3, const float* b3, const float* w5, const float* b5, const float* w7, const float* b7,
                                    const float* a, const float* kmax, const float* ksum, const float* Mmat,
@@ -1423,8 +1143,8 @@ extern "C" int mdvit_factoratt_bwd(const float* dout, const float* qkv, const fl
     hipStream_t s = (hipStream_t)stream;
     FaGeom g;
     MDVIT_CHECK_ARG(make_geom(g, B, H, W, C, heads, s3, s5, s7), MDVIT_E_SHAPE, "factoratt_bwd: bad geometry B=%d H=%d W=%d C=%d heads=%d", B, H, W, C, heads);
+    FA_CHECK_BUILT("factoratt_bwd", g);
     MDVIT_CHECK_ARG(ws_bytes >= fa_ws_floats(B, g.N, C, heads) * sizeof(float), MDVIT_E_WORKSPACE, "factoratt_bwd: workspace too small (%zu bytes)", ws_bytes);
-    MDVIT_CHECK_ARG(C <= 512, MDVIT_E_SHAPE, "factoratt_bwd: C=%d > 512 not built", C);
     MDVIT_CHECK_ARG((a == nullptr) == (e == nullptr), MDVIT_E_SHAPE, "factoratt_bwd: a and e must both be given or both be NULL");
     const int Ch = g.Ch, NT = cdiv(g.N, FA_T);
     float* dU = (float*)ws;
@@ -1447,29 +1167,19 @@ extern "C" int mdvit_factoratt_bwd(const float* dout, const float* qkv, const fl
         return mdvit_reduce_partials_batched(e_part, B, gx, C, e, s);
     }
     // 1 + 2: dM = Q^T (scale * a * G) as tile partials, and on the same staged tiles dU = a G q and the e partial rows
-    const int GWp = Ch < 32 ? 32 : Ch;
-    MDVIT_CHECK_ARG(C % GWp == 0, MDVIT_E_SHAPE, "factoratt_bwd: C=%d is not a multiple of the %d-channel group", C, GWp);
-    const int NSUBb = fa_nsub(NT, C / GWp, B), NTS = cdiv(NT, NSUBb);
+    const int NSUBb = fa_nsub(NT), NTS = cdiv(NT, NSUBb);
     float* e_part = ws_P + (long)B * NT * C * Ch;               // [B][NTS][C] partial rows (the region is reused by the window-weight gradients below)
-    {
-#define FA_PART_LAUNCH(CHV) hipLaunchKernelGGL((fa_partial_kernel<CHV, false>), dim3(NTS, C / GWp, B), dim3(256), 0, s, \
+#define FA_PART_STREAM(CHV) fa_partial_stream_launch<CHV, false>(dim3(NTS, 1, B), s, qkv, (long)3 * C, dout, (long)C, a, g.scale, nullptr, nullptr, ws_P, g, NT, NSUBb, out, dU, e ? e_part : nullptr)
+#define FA_PART_TILES(CHV) hipLaunchKernelGGL((fa_partial_kernel<CHV, false>), dim3(NTS, C / CHV, B), dim3(256), 0, s, \
                        qkv, (long)3 * C, dout, (long)C, a, g.scale, (float*)nullptr, (float*)nullptr, ws_P, g, NT, NSUBb, out, dU, e ? e_part : (float*)nullptr)
-        static const bool s8p_env = [] { const char* e = getenv("MDVIT_FA_PARTIAL_STREAM"); return !(e && e[0] == '0'); }();
-        static const bool s16p_env = [] { const char* e = getenv("MDVIT_FA_PARTIAL_STREAM16"); return !(e && e[0] == '0'); }();
-        if (Ch == 8 && C == 64 && s8p_env)
-            fa_partial_stream_launch<8, false>(dim3(NTS, 1, B), s, qkv, (long)3 * C, dout, (long)C, a, g.scale, nullptr, nullptr, ws_P, g, NT, NSUBb, out, dU, e ? e_part : nullptr);
-        else if (Ch == 16 && C == 128 && s8p_env && s16p_env)
-            fa_partial_stream_launch<16, false>(dim3(NTS, 1, B), s, qkv, (long)3 * C, dout, (long)C, a, g.scale, nullptr, nullptr, ws_P, g, NT, NSUBb, out, dU, e ? e_part : nullptr);
-        else
-        switch (Ch) {
-            case 8: FA_PART_LAUNCH(8); break;
-            case 16: FA_PART_LAUNCH(16); break;
-            case 40: FA_PART_LAUNCH(40); break;
-            case 64: FA_PART_LAUNCH(64); break;
-            default: return mdvit_set_error(MDVIT_E_SHAPE, "factoratt_bwd: head dim %d not built (8/16/40/64)", Ch);
-        }
-#undef FA_PART_LAUNCH
+    switch (Ch) {          // (fa_built: no other head dim gets here)
+        case 8: FA_PART_STREAM(8); break;
+        case 16: FA_PART_STREAM(16); break;
+        case 40: FA_PART_TILES(40); break;
+        case 64: FA_PART_TILES(64); break;
     }
+#undef FA_PART_STREAM
+#undef FA_PART_TILES
     if (e) {
         const int rc = mdvit_reduce_partials_batched(e_part, B, NTS, C, e, s);
         if (rc != MDVIT_OK) return rc;
@@ -1491,62 +1201,25 @@ extern "C" int mdvit_factoratt_bwd(const float* dout, const float* qkv, const fl
         launch_conv3<true>(dU, (long)C, off, ws3, nullptr, dVc, (long)C, off, cg, ncls, s);
     }
     // 4, 5
-    const int GW = Ch < 32 ? 32 : Ch;
-    MDVIT_CHECK_ARG(C % GW == 0, MDVIT_E_SHAPE, "factoratt_bwd: C=%d is not a multiple of the %d-channel group", C, GW);
-    const int ntiles = cdiv(g.N, 32);
     if (Ch >= 32) {                                // products dealt to wavefronts: 2 tiles x 3 roles per workgroup pass
         // 8 tiles per workgroup (4 per wave slot) amortise the staging of the two Ch x Ch matrices; fewer only while the grid would not reach one workgroup per CU
         // (measured at 32 images, C = 320 / 512: 2 tiles 227 / 157 us, 4: 163 / 97, 8: 144 / 71, 32: 140 / 71)
+        const int ntiles = cdiv(g.N, 32);
         int tpb = 8;
-        while (tpb > 2 && (long)cdiv(ntiles, tpb) * (C / GW) * B < 256) tpb /= 2;
-        if (g_fa_apply_tiles > 0) tpb = g_fa_apply_tiles;
+        while (tpb > 2 && (long)cdiv(ntiles, tpb) * heads * B < 256) tpb /= 2;
         const int gx = cdiv(ntiles, tpb);
-        const long nwg = (long)gx * (C / GW) * B;
-        static const bool xcd_env = [] { const char* e = getenv("MDVIT_FA_APPLY3_XCD"); return !(e && e[0] == '0'); }();
-        const int xcd_map = xcd_env && nwg % 8 == 0 && nwg < (1L << 30);          // (see the kernel: the heads of a token range on one XCD)
-        dim3 grid = xcd_map ? dim3((unsigned)nwg, 1, 1) : dim3(gx, C / GW, B);
+        const long nwg = (long)gx * heads * B;
+        const int xcd_map = nwg % 8 == 0 && nwg < (1L << 30);          // (see the kernel: the heads of a token range on one XCD)
+        dim3 grid = xcd_map ? dim3((unsigned)nwg, 1, 1) : dim3(gx, heads, B);
         if (Ch == 40) hipLaunchKernelGGL((fa_bwd_apply3_kernel<40>), grid, dim3(384), 0, s, dout, qkv, U, dVc, Mmat, a, kmax, ksum, ws_P, NTS, dqkv, g, tpb, gx, xcd_map);
-        else if (Ch == 64) hipLaunchKernelGGL((fa_bwd_apply3_kernel<64>), grid, dim3(384), 0, s, dout, qkv, U, dVc, Mmat, a, kmax, ksum, ws_P, NTS, dqkv, g, tpb, gx, xcd_map);
-        else return mdvit_set_error(MDVIT_E_SHAPE, "factoratt_bwd: head dim %d not built (8/16/40/64)", Ch);
-        MDVIT_LAUNCH_CHECK();
-        return MDVIT_OK;
-    }
-    static const bool s8_env = [] { const char* e = getenv("MDVIT_FA_APPLY_STREAM"); return !(e && e[0] == '0'); }();
-    if (Ch == 8 && C == 64 && s8_env && g_fa_apply_mode == 0) {          // the streaming VALU form (MDVIT_FA_APPLY_STREAM=0: the MFMA tiles, A/B)
-        int tpbk = 1024;                                              // tokens per workgroup: halved while the launch has fewer than two workgroups per CU
+        else hipLaunchKernelGGL((fa_bwd_apply3_kernel<64>), grid, dim3(384), 0, s, dout, qkv, U, dVc, Mmat, a, kmax, ksum, ws_P, NTS, dqkv, g, tpb, gx, xcd_map);
+    } else {                                       // the streaming VALU form
+        int tpbk = Ch == 8 ? 1024 : 512;           // tokens per workgroup: halved while the launch has fewer than two workgroups per CU
         while (tpbk > 128 && (long)cdiv(g.N, tpbk) * B < 512) tpbk /= 2;
-        if (g_fa_apply_tiles > 0) tpbk = 32 * g_fa_apply_tiles;
-        // the Ch = 8 matrices in the LDS table too (214.8 against 221.7 us at 32 images with them in 96 registers; MDVIT_FA_APPLY_S8_TABLE=0: the register form, A/B)
-        static const bool s8_tab = [] { const char* e = getenv("MDVIT_FA_APPLY_S8_TABLE"); return !(e && e[0] == '0'); }();
-        if (s8_tab) hipLaunchKernelGGL(fa_bwd_apply_tab_kernel<8>, dim3(cdiv(g.N, tpbk), B), dim3(256), 0, s, dout, qkv, U, dVc, Mmat, a, kmax, ksum, ws_P, NTS, dqkv, g, tpbk);
-        else hipLaunchKernelGGL(fa_bwd_apply_s8_kernel, dim3(cdiv(g.N, tpbk), B), dim3(256), 0, s, dout, qkv, U, dVc, Mmat, a, kmax, ksum, ws_P, NTS, dqkv, g, tpbk);
-        MDVIT_LAUNCH_CHECK();
-        return MDVIT_OK;
+        const dim3 grid(cdiv(g.N, tpbk), B);
+        if (Ch == 8) hipLaunchKernelGGL(fa_bwd_apply_tab_kernel<8>, grid, dim3(256), 0, s, dout, qkv, U, dVc, Mmat, a, kmax, ksum, ws_P, NTS, dqkv, g, tpbk);
+        else hipLaunchKernelGGL(fa_bwd_apply_tab_kernel<16>, grid, dim3(256), 0, s, dout, qkv, U, dVc, Mmat, a, kmax, ksum, ws_P, NTS, dqkv, g, tpbk);
     }
-    static const bool s16_env = [] { const char* e = getenv("MDVIT_FA_APPLY_STREAM16"); return !(e && e[0] == '0'); }();
-    if (Ch == 16 && C == 128 && s8_env && s16_env && g_fa_apply_mode == 0) {
-        int tpbk = 512;
-        while (tpbk > 128 && (long)cdiv(g.N, tpbk) * B < 512) tpbk /= 2;
-        if (g_fa_apply_tiles > 0) tpbk = 32 * g_fa_apply_tiles;
-        hipLaunchKernelGGL(fa_bwd_apply_tab_kernel<16>, dim3(cdiv(g.N, tpbk), B), dim3(256), 0, s, dout, qkv, U, dVc, Mmat, a, kmax, ksum, ws_P, NTS, dqkv, g, tpbk);
-        MDVIT_LAUNCH_CHECK();
-        return MDVIT_OK;
-    }
-    int tpb = 4;                                   // 32-token tiles per block (one per wavefront), doubled while the grid stays large
-    while (tpb < 64 && (long)cdiv(ntiles, tpb * 2) * (C / GW) * B >= 2048) tpb *= 2;
-    if (g_fa_apply_tiles > 0) tpb = g_fa_apply_tiles;
-    dim3 grid(cdiv(ntiles, tpb), C / GW, B);
-#define FA_BWD_LAUNCH(CHV, MODEV) hipLaunchKernelGGL((fa_bwd_apply_kernel<CHV, MODEV>), grid, dim3(256), 0, s, dout, qkv, U, dVc, Mmat, a, kmax, ksum, ws_P, NTS, dqkv, g, tpb)
-    switch (Ch * 4 + g_fa_apply_mode) {
-        case 8 * 4 + 0: FA_BWD_LAUNCH(8, 0); break;
-        case 8 * 4 + 1: FA_BWD_LAUNCH(8, 1); break;
-        case 8 * 4 + 2: FA_BWD_LAUNCH(8, 2); break;
-        case 16 * 4 + 0: FA_BWD_LAUNCH(16, 0); break;
-        case 16 * 4 + 1: FA_BWD_LAUNCH(16, 1); break;
-        case 16 * 4 + 2: FA_BWD_LAUNCH(16, 2); break;
-        default: return mdvit_set_error(MDVIT_E_SHAPE, "factoratt_bwd: head dim %d not built (8/16/40/64)", Ch);
-    }
-#undef FA_BWD_LAUNCH
     MDVIT_LAUNCH_CHECK();
     return MDVIT_OK;
 }

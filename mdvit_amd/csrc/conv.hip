@@ -919,9 +919,8 @@ extern "C" int mdvit_dwconv3x3_bwd(const float* dy, const float* x, const float*
 extern "C" int mdvit_gconv2_3x3_fwd(const float* skip, const float* up, const float* w, float* y, int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
     MDVIT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && C <= 2048, MDVIT_E_SHAPE, "gconv2_fwd: bad shape B=%d H=%d W=%d C=%d", B, H, W, C);
     const long total = (long)B * H * W * C / 2;
-    static const bool tiled = [] { const char* e = getenv("MDVIT_GCONV2_TILES"); return !(e && e[0] == '0'); }();          // 0: the element-per-thread kernels (A/B)
     const int tiles_w = cdiv(W, CT_TW), tiles = tiles_w * cdiv(H, CT_TH);
-    if (tiled && C % 32 == 0 && aligned16(skip) && aligned16(up) && B <= 65535)
+    if (C % 32 == 0 && aligned16(skip) && aligned16(up) && B <= 65535)          // the LDS tiles; other shapes: the element-per-thread kernel
         hipLaunchKernelGGL((gconv2_tile_kernel<false>), dim3(tiles, 2 * C / CT_CL, B), dim3(256), 0, (hipStream_t)stream, skip, up, w, y, (float*)nullptr, H, W, C, tiles_w);
     else
         hipLaunchKernelGGL(gconv2_fwd_kernel, dim3(ew_grid(total)), dim3(256), sizeof(float) * 18 * C, (hipStream_t)stream, skip, up, w, y, B, H, W, C);
@@ -935,9 +934,8 @@ extern "C" int mdvit_gconv2_3x3_bwd(const float* dy, const float* skip, const fl
     MDVIT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && C <= 1024, MDVIT_E_SHAPE, "gconv2_bwd: bad shape B=%d H=%d W=%d C=%d", B, H, W, C);
     const long total = (long)B * H * W * C / 2;
     MDVIT_CHECK_ARG((dskip == nullptr) == (dup == nullptr), MDVIT_E_SHAPE, "gconv2_bwd: dskip and dup go together");
-    static const bool tiled = [] { const char* e = getenv("MDVIT_GCONV2_TILES"); return !(e && e[0] == '0'); }();
     const int tiles_w = cdiv(W, CT_TW), tiles = tiles_w * cdiv(H, CT_TH);
-    if (dskip && tiled && C % 64 == 0 && aligned16(dy) && B <= 65535)          // (C % 64: a 32-channel concat block reads 16 dy channels = whole float4 quads of one source half)
+    if (dskip && C % 64 == 0 && aligned16(dy) && B <= 65535)          // (C % 64: a 32-channel concat block reads 16 dy channels = whole float4 quads of one source half)
         hipLaunchKernelGGL((gconv2_tile_kernel<true>), dim3(tiles, 2 * C / CT_CL, B), dim3(256), 0, s, dy, (const float*)nullptr, w, dskip, dup, H, W, C, tiles_w);
     else if (dskip) hipLaunchKernelGGL(gconv2_dgrad_kernel, dim3(ew_grid(total)), dim3(256), sizeof(float) * 18 * C, s, dy, w, dskip, dup, B, H, W, C);
     if (dw) {
@@ -1075,8 +1073,7 @@ extern "C" int mdvit_upsample_multi_fwd(const float* const* xs, const int32_t* H
     }
     MDVIT_CHECK_ARG(aligned16(y) && (!base || aligned16(base)), MDVIT_E_ALIGN, "upsample_multi_fwd: y / base must be 16-byte aligned");
     {   // the LDS-tiled kernel where the shape allows it (the peer heads: 128 x 128 x 512 from 64 / 32 / 16)
-        static const bool tile_on = !(getenv("MDVIT_UPSAMPLE_TILED") && atoi(getenv("MDVIT_UPSAMPLE_TILED")) == 0);
-        bool ok = tile_on && Ho % UT_H == 0 && Wo % UT_W == 0 && C % UT_C == 0 && (long)(Ho / UT_H) * (Wo / UT_W) < (1L << 30) && C / UT_C < 65536 && B < 65536;
+        bool ok = Ho % UT_H == 0 && Wo % UT_W == 0 && C % UT_C == 0 && (long)(Ho / UT_H) * (Wo / UT_W) < (1L << 30) && C / UT_C < 65536 && B < 65536;
         int pool = 0;
         for (int i = 0; i < n && ok; ++i) {
             // power-of-two factors only: for them a tile's source patch is at most tile / factor + 2 rows (columns) -- the bound the pool is sized with; a factor of 3
@@ -1123,8 +1120,7 @@ extern "C" int mdvit_upsample_multi_bwd(const float* dy, float* const* dxs, cons
     const long cq = C / 4;
     const int bpr = (int)cdiv((long)wsum * cq, 256L);
     MDVIT_CHECK_ARG((long)B * Ho * bpr < (1L << 31), MDVIT_E_SHAPE, "upsample_multi_bwd: too many workgroups");
-    static const bool lds_rows = [] { const char* e = getenv("MDVIT_UPSAMPLE_BWD_LDS"); return !(e && e[0] == '0'); }();          // 0: the L2 re-reading kernel (A/B)
-    if (lds_rows && C % 32 == 0 && Wo <= 384 && (long)B * Ho < (1L << 31) && C / 32 <= 65535)
+    if (C % 32 == 0 && Wo <= 384 && (long)B * Ho < (1L << 31) && C / 32 <= 65535)          // the output row in LDS; other shapes: the L2 re-reading kernel
         hipLaunchKernelGGL(upsample_multi_bwd_w_lds_kernel, dim3((unsigned)((long)B * Ho), C / 32), dim3(256), sizeof(float) * Wo * 32, s, p, dy, Wo, C);
     else
         hipLaunchKernelGGL(upsample_multi_bwd_w_kernel, dim3((unsigned)((long)B * Ho * bpr)), dim3(256), 0, s, p, dy, (long)B * Ho, Wo, C, bpr);

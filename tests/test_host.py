@@ -36,6 +36,14 @@ def test_bad_arguments_return_error_codes_without_gpu():
     assert b"gemm" in lib.mdvit_last_error()
     assert lib.mdvit_stemconv_fwd(None, None, None, 1, 8, 8, 4, 32, None) == 1
     assert b"in_chans" in lib.mdvit_last_error()
+    # the attention core is built for 8 heads at C = 64 / 128 and head dim 40 / 64 with C <= 512: anything else is refused by name, forward and backward, before any launch
+    for (Cn, heads, splits) in ((32, 4, (1, 1, 2)), (128, 16, (4, 6, 6)), (64, 4, (1, 1, 2)), (256, 16, (4, 6, 6)), (96, 8, (2, 3, 3)), (640, 10, (2, 4, 4))):
+        assert lib.mdvit_factoratt_fwd(*[None] * 13, None, 1 << 40, 1, 8, 8, Cn, heads, *splits, None) == 1, (Cn, heads)
+        msg = lib.mdvit_last_error()
+        assert b"factoratt_fwd" in msg and b"not built" in msg and b"64 / 128" in msg and b"320 / 512" in msg, msg
+        assert lib.mdvit_factoratt_bwd(*[None] * 22, None, 1 << 40, 1, 8, 8, Cn, heads, *splits, None) == 1, (Cn, heads)
+        msg = lib.mdvit_last_error()
+        assert b"factoratt_bwd" in msg and b"not built" in msg and b"64 / 128" in msg and b"320 / 512" in msg, msg
 
 
 def test_launch_sampler_is_off_and_empty_without_launches():
