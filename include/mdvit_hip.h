@@ -711,6 +711,31 @@ int mdvit_structure_loss_fwd(const float* pred, const float* mask, const float* 
 int mdvit_structure_loss_bwd(const float* pred, const float* mask, const float* weit, const double* sums, const float* gscale, float* dpred, int32_t B, int64_t HW,
                              void* stream);
 
+/* ---- squeeze-excite adapters of BASE_DASE / BASE_USE (Models/Sota_adapters/base_sota_adapt.py:273-637; csrc/se_adapter.hip) ----------------------
+ * x [B, N, C] tokens, C % 4 == 0, C <= 1024; p[b,c] = mean_n x[b,n,c].
+ *   MDVIT_SE_DASE (DomainAttention, domain_attention_module.py:50-66; K = 4 SELayer branches without their sigmoid, r = C / 16):
+ *       w = softmax_k(Wg p + bg), z_k = W2_k relu(W1_k p + b1_k) + b2_k, s = sigmoid(sum_k w_k z_k), y = x * s.
+ *       The branch weights are passed STACKED: W1 [K, r, C], b1 [K, r], W2 [K, C, r], b2 [K, C]; Wg [K, C], bg [K] (fc_1).
+ *   MDVIT_SE_USE (SEBlock, base_sota_adapt.py:628-637; one SELayer with its sigmoid, r = C / 8): s = sigmoid(W2 relu(W1 p + b1) + b2), y = x * s + x.
+ *       W1 [r, C], b1 [r], W2 [C, r], b2 [C]; Wg / bg NULL.
+ * At most 512 hidden units (K * r).  save: mdvit_se_adapter_save_bytes(d) bytes, written by _fwd and read by _bwd (p, the hidden pre-activations, w, z_k, s:
+ * O(B C)).  ws: mdvit_se_adapter_ws_bytes(d) bytes of scratch for either call -- the size depends on the descriptor alone, not on which outputs are asked for.
+ * Backward: ds[b,c] = sum_n g x, the gate's backward gives dp and the parameter gradients (OVERWRITTEN; each may be NULL: not computed),
+ * dx = g * gate + dp / N; dx == NULL is legal (nothing is written for it).  Every sum has a fixed order (token slabs of 128, then samples in batch
+ * order): no atomics, two calls on the same input agree bit for bit.  The two size functions return 0 for a descriptor the kernels are not built for. */
+enum { MDVIT_SE_DASE = 0, MDVIT_SE_USE = 1 };
+typedef struct MdvitSeAdapterDesc {
+    int32_t kind;
+    int32_t B, N, C, r;
+    const float* W1; const float* b1; const float* W2; const float* b2;
+    const float* Wg; const float* bg;
+} MdvitSeAdapterDesc;
+size_t mdvit_se_adapter_save_bytes(const MdvitSeAdapterDesc* d);
+size_t mdvit_se_adapter_ws_bytes(const MdvitSeAdapterDesc* d);
+int mdvit_se_adapter_fwd(const MdvitSeAdapterDesc* d, const float* x, float* y, float* save, void* ws, size_t ws_bytes, void* stream);
+int mdvit_se_adapter_bwd(const MdvitSeAdapterDesc* d, const float* g, const float* x, const float* save, float* dx, float* dW1, float* db1, float* dW2,
+                         float* db2, float* dWg, float* dbg, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """mdvit_amd -- MI355X-native (gfx950 HIP) forward/backward path of MDViT behind the reference's
 nn.Module call surface.  See DESIGN.md / INTEGRATION.md."""
-from .model import BASE, BASE_DSN, MDViT, MDViT_DSN  # noqa: F401
+from .model import BASE, BASE_DASE, BASE_DSN, BASE_USE, MDViT, MDViT_DSN  # noqa: F401
 from .losses import domain_losses, seg_loss  # noqa: F401
 
 
@@ -13,4 +13,4 @@ def load_reference_state_dict(model, state_dict, strict: bool = True):
     return model.load_state_dict(sd, strict=strict)
 
 
-__all__ = ["MDViT", "MDViT_DSN", "BASE", "BASE_DSN", "domain_losses", "seg_loss", "load_reference_state_dict"]
+__all__ = ["MDViT", "MDViT_DSN", "BASE", "BASE_DSN", "BASE_DASE", "BASE_USE", "domain_losses", "seg_loss", "load_reference_state_dict"]

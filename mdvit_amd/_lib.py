@@ -101,6 +101,13 @@ class BlockGrads(C.Structure):
     _fields_ = [(n, vp) for n in BLOCK_PARAMS] + [("accumulate", i32), ("dgrad_only", i32), ("aux_first", i32), ("ln_accumulate", i32), ("e_out", vp)]
 
 
+class SeAdapterDesc(C.Structure):
+    _fields_ = [("kind", i32), ("B", i32), ("N", i32), ("C", i32), ("r", i32), ("W1", vp), ("b1", vp), ("W2", vp), ("b2", vp), ("Wg", vp), ("bg", vp)]
+
+
+SE_DASE, SE_USE = 0, 1
+
+
 class BlockStreams(C.Structure):
     _fields_ = [("main", vp), ("side", vp), ("events", C.POINTER(vp)), ("n_events", i32), ("next_event", C.POINTER(i32))]
 
@@ -234,6 +241,8 @@ _SIGS = {
     "mdvit_seg_losses_groups_sums": [vp, vp, vp, vp, i64, i32, vp],
     "mdvit_seg_losses_groups_final": [vp, vp, vp, i64, i32, i32, vp],
     "mdvit_seg_losses_groups_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, vp],
+    "mdvit_se_adapter_fwd": [C.POINTER(SeAdapterDesc), vp, vp, vp, vp, C.c_size_t, vp],
+    "mdvit_se_adapter_bwd": [C.POINTER(SeAdapterDesc)] + [vp] * 10 + [vp, C.c_size_t, vp],
 }
 
 _lib = None
@@ -318,6 +327,10 @@ def _attach_prototypes(lib):
     lib.mdvit_da_ws_bytes.argtypes = [i32, i32, i32]
     lib.mdvit_da_many_ws_bytes.restype = C.c_size_t
     lib.mdvit_da_many_ws_bytes.argtypes = [C.POINTER(DaMany), i32]
+    lib.mdvit_se_adapter_save_bytes.restype = C.c_size_t
+    lib.mdvit_se_adapter_save_bytes.argtypes = [C.POINTER(SeAdapterDesc)]
+    lib.mdvit_se_adapter_ws_bytes.restype = C.c_size_t
+    lib.mdvit_se_adapter_ws_bytes.argtypes = [C.POINTER(SeAdapterDesc)]
     for name, sig in _SIGS.items():
         try:
             fn = getattr(lib, name)

@@ -6,11 +6,14 @@ Call surface kept (multi_train_MDViT.py:57-60,140-146; multi_train_BASE.py:66-68
   MDViT(img_size=..., drop_rate=0.1, drop_path_rate=0.1, conv_norm=nn.BatchNorm2d, adapt_method='Sup',
         num_domains=4, decoder_name='MLPFM');  out, aux = model(img, domain_label, d)  |  model(img, d=d)
   BASE(drop_rate, drop_path_rate, conv_norm, adapt_method);  out = model(img)
+  BASE_DASE / BASE_USE <- Models/Sota_adapters/base_sota_adapt.py:273-448 / 451-637: BASE's trunk with squeeze-excite adapters (mdvit_amd.adapters) behind
+  every encoder stage and decoder block;  BASE_DASE(drop_rate, drop_path_rate, conv_norm);  out = model(img)
 Inputs NCHW fp32 on the GPU; outputs (B,1,H,W) fp32 logits.
 """
 from __future__ import annotations
 
 import os
+from functools import partial
 from typing import Optional
 
 import torch
@@ -18,6 +21,7 @@ from torch import nn
 
 from . import ops
 from ._lib import ACT_RELU
+from .adapters import DomainAttention, SEBlock
 from .blocks import (droppath_pool, dsn_domain, BatchNormAct, Conv2d_BN, ConvParams, DWCPatchEmbed, MHSA_stage_adapt, _NoParams, _check_norm,
                      init_weights_)
 from .decode import DeepLabV3Decoder, MLPDecoder, MLPDecoderFM, UnetDecodingBlockTransformer
@@ -28,6 +32,11 @@ _FORK_GROUPS = os.environ.get("MDVIT_FORK_GROUPS", "1") != "0"      # the peer h
 class _EncoderDecoder(nn.Module):
     _base_semantics = False
     _dsn = 0            # > 0: domain-specific norms (MDViT_DSN): that many norms per BatchNorm / LayerNorm site
+    # hook points of the trunk for models that put an adapter behind its blocks (BASE_DASE / BASE_USE); None: the trunk as it is
+    _encoder_adapter = None          # (stage index, stage output NHWC) -> adapted tensor
+    _adapt_skip_only = False         # True: the adapted tensor feeds the skip path / bridge only, the next stage takes the stage output itself
+    _bridge_adapter_fn = None        # (bridge output) -> adapted tensor
+    _decoder_adapter = None          # (decoder index 0..3, decoder output) -> adapted tensor
 
     def _build_trunk(self, img_size, in_chans, num_stages, num_layers, embed_dims, mlp_ratios, num_heads, qkv_bias, qk_scale,
                      drop_rate, attn_drop_rate, drop_path_rate, norm_layer, conv_norm, adapt_method, num_domains, dsn=0):
@@ -106,7 +115,13 @@ class _EncoderDecoder(nn.Module):
             if idx == 0 and self._has_aux_first:
                 x = ops.aux_stop(x)          # the aux (data-gradient-only) sweep ends at the first adapter: the stem / patch embed carry none
             x = self.mhsa_stages[idx](x.view(B, H * W, Cn), H, W, domain_label).view(B, H, W, Cn)
-            if head_groups > 1:
+            if self._encoder_adapter is not None:
+                if self._adapt_skip_only and idx < self.num_stages - 1:          # base_sota_adapt.py:596-599
+                    x, a_ = ops.fork(x, 2)
+                    s_, e_ = ops.fork(self._encoder_adapter(idx, a_), 2)
+                else:                                                            # :419-423 (and the last stage of :596-605: only the bridge follows)
+                    x, s_, e_ = ops.fork(self._encoder_adapter(idx, x), 3)
+            elif head_groups > 1:
                 x, s_, e_ = ops.fork_groups(x, 2, head_groups)
             else:
                 x, s_, e_ = ops.fork(x, 3)
@@ -120,14 +135,16 @@ class _EncoderDecoder(nn.Module):
             out = self.bridge[1](out)
             out = ops.conv3x3_dense(out, self.bridge[3].weight, self.bridge[3].bias, 1)
             out = self.bridge[4](out)
+        if self._bridge_adapter_fn is not None:
+            out = self._bridge_adapter_fn(out)
         if getattr(self, "decoder_name", None) == "Transformer":
             out, bridge_out = ops.fork(out, 2)          # the per-domain transformer peers start from the bridge output too
         else:
             bridge_out = out
-        out = self.decoder1(out, skip[3], domain_label)
-        out = self.decoder2(out, skip[2], domain_label)
-        out = self.decoder3(out, skip[1], domain_label)
-        out = self.decoder4(out, skip[0], domain_label)
+        for j, dec in enumerate((self.decoder1, self.decoder2, self.decoder3, self.decoder4)):
+            out = dec(out, skip[3 - j], domain_label)
+            if self._decoder_adapter is not None:
+                out = self._decoder_adapter(j, out)
         if head_groups > 1:
             out, dec4 = ops.fork_groups(out, 1, head_groups)
         else:
@@ -362,3 +379,65 @@ class BASE_DSN(BASE):
         if out_feat:
             return {"seg": logits, "feat": self._pooled_feat(enc[3])}
         return logits
+
+
+class _BASE_SEAdapted(_EncoderDecoder):
+    """BASE's trunk (no Domain Adapter in the blocks) with one squeeze-excite adapter behind every encoder stage and every decoder block; the subclasses pick
+    the adapter.  forward(x, out_feat=False, out_seg=True) as the reference; extension: groups=G runs a DOMAIN-BATCHED forward -- x holds G equal consecutive
+    domain batches and BatchNorm keeps its statistics per batch (the adapters are per sample), so the result equals G forwards concatenated."""
+    _base_semantics = True
+
+    def _build(self, img_size, in_chans, num_stages, num_layers, embed_dims, mlp_ratios, num_heads, qkv_bias, qk_scale, drop_rate, attn_drop_rate,
+               drop_path_rate, norm_layer, conv_norm, make_adapter):
+        self._build_trunk(img_size, in_chans, num_stages, num_layers, embed_dims, mlp_ratios, num_heads, qkv_bias, qk_scale,
+                          drop_rate, attn_drop_rate, drop_path_rate, norm_layer, conv_norm, None, 4)
+        E = list(embed_dims)
+        self.encoder_adapters = nn.ModuleList([make_adapter(E[i]) for i in range(num_stages)])
+        self.decoder_adapters = nn.ModuleList([make_adapter(E[-i - 1]) for i in range(num_stages)])
+
+    def _encoder_adapter(self, idx, x):
+        return self.encoder_adapters[idx](x)
+
+    def _decoder_adapter(self, j, x):
+        return self.decoder_adapters[j](x)
+
+    def forward(self, x, out_feat=False, out_seg=True, groups: int = 1):
+        if x.shape[0] % groups:
+            raise ValueError(f"batch {x.shape[0]} is not {groups} equal domain batches")
+        logits, enc, _, _, _ = self._trunk(x, None, groups=groups)
+        if not out_seg:
+            return {"seg": None, "feat": self._pooled_feat(enc[3])}
+        if out_feat:
+            return {"seg": logits, "feat": self._pooled_feat(enc[3])}
+        return logits
+
+
+class BASE_DASE(_BASE_SEAdapted):
+    """base_sota_adapt.py:273-448: domain-attentive SE adapters (DomainAttention, reduction 16).  The adapted tensor REPLACES the stage output: the next stage,
+    the skip path and the bridge all read it (:419-423)."""
+
+    def __init__(self, img_size=512, in_chans=3, num_stages=4, num_layers=[2, 2, 2, 2], embed_dims=[64, 128, 320, 512],
+                 mlp_ratios=[8, 8, 4, 4], num_heads=[8, 8, 8, 8], qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0,
+                 drop_path_rate=0.0, norm_layer=partial(nn.LayerNorm, eps=1e-6), conv_norm=nn.BatchNorm2d, **kwargs):
+        super().__init__()
+        self._build(img_size, in_chans, num_stages, num_layers, embed_dims, mlp_ratios, num_heads, qkv_bias, qk_scale, drop_rate, attn_drop_rate,
+                    drop_path_rate, norm_layer, conv_norm, lambda c: DomainAttention(c, reduction=16))
+        init_weights_(self)
+
+
+class BASE_USE(_BASE_SEAdapted):
+    """base_sota_adapt.py:451-637: USE-Net residual SE adapters (SEBlock, reduction 8).  The encoder adapter sits on the SKIP path only (:596-599): the next stage
+    takes the un-adapted stage output; the bridge reads the adapted stage 3 (:605) and has an adapter of its own behind it (:606)."""
+    _adapt_skip_only = True
+
+    def __init__(self, img_size=512, in_chans=3, num_stages=4, num_layers=[2, 2, 2, 2], embed_dims=[64, 128, 320, 512],
+                 mlp_ratios=[8, 8, 4, 4], num_heads=[8, 8, 8, 8], qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0,
+                 drop_path_rate=0.0, norm_layer=partial(nn.LayerNorm, eps=1e-6), conv_norm=nn.BatchNorm2d, **kwargs):
+        super().__init__()
+        self._build(img_size, in_chans, num_stages, num_layers, embed_dims, mlp_ratios, num_heads, qkv_bias, qk_scale, drop_rate, attn_drop_rate,
+                    drop_path_rate, norm_layer, conv_norm, lambda c: SEBlock(c, reduction=8))
+        self.bridge_adapter = SEBlock(embed_dims[3] * 2, reduction=8)
+        init_weights_(self)
+
+    def _bridge_adapter_fn(self, x):
+        return self.bridge_adapter(x)

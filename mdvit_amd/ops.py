@@ -2398,6 +2398,100 @@ def rowdot(x, w, b=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# Squeeze-excite adapters (BASE_DASE / BASE_USE, base_sota_adapt.py:273-637; csrc/se_adapter.hip)
+SE_KINDS = {"dase": _lib.SE_DASE, "use": _lib.SE_USE}
+
+
+def _se_desc(kind, B, N, Cn, r, W1, b1, W2, b2, Wg, bg):
+    d = _lib.SeAdapterDesc()
+    d.kind, d.B, d.N, d.C, d.r = kind, B, N, Cn, r
+    d.W1, d.b1, d.W2, d.b2, d.Wg, d.bg = _p(W1), _p(b1), _p(W2), _p(b2), _p(Wg), _p(bg)
+    return d
+
+
+def _se_sizes(d):
+    lib = _lib.load()
+    save, ws = lib.mdvit_se_adapter_save_bytes(C.byref(d)), lib.mdvit_se_adapter_ws_bytes(C.byref(d))
+    if not save or not ws:
+        raise _lib.MdvitHipError("se_adapter: " + lib.mdvit_last_error().decode(errors="replace"))
+    return save, ws
+
+
+class _SeAdapter(torch.autograd.Function):
+    """y = x * gate(mean_tokens x).  params, USE: (W1, b1, W2, b2); DASE: (Wg, bg) + the four branches' (W1_k, b1_k, W2_k, b2_k), k = 0..3 -- separate
+    Parameters (the reference's state_dict), stacked for the kernels here and their gradients handed back as views of the stacked gradient."""
+
+    @staticmethod
+    def forward(ctx, x, kind, *params):
+        ctx.set_materialize_grads(False)
+        _chk(x, *params)
+        if x.dim() != 3:
+            raise _lib.MdvitHipError("se_adapter: x must be [B, N, C] tokens")
+        B, N, Cn = x.shape
+        if kind == _lib.SE_DASE:
+            if len(params) != 18:
+                raise _lib.MdvitHipError("se_adapter: DASE takes (Wg, bg) and four (W1, b1, W2, b2) branches")
+            Wg, bg = params[0], params[1]
+            with torch.no_grad():
+                W1, b1, W2, b2 = (torch.stack([params[2 + 4 * k + i] for k in range(4)]) for i in range(4))
+        elif kind == _lib.SE_USE:
+            if len(params) != 4:
+                raise _lib.MdvitHipError("se_adapter: USE takes (W1, b1, W2, b2)")
+            (W1, b1, W2, b2), Wg, bg = params, None, None
+        else:
+            raise _lib.MdvitHipError(f"se_adapter: unknown kind {kind!r}")
+        r = W1.shape[-2]
+        d = _se_desc(kind, B, N, Cn, r, W1, b1, W2, b2, Wg, bg)
+        save_b, ws_b = _se_sizes(d)
+        y = _empty_like(x)
+        save = _empty((save_b // 4,), device=x.device, dtype=torch.float32)
+        ws = torch.empty((ws_b // 4,), device=x.device, dtype=torch.float32)
+        call("mdvit_se_adapter_fwd", C.byref(d), _p(x), _p(y), _p(save), _p(ws), ws_b, _stream())
+        ctx.save_for_backward(x, save, W1, b1, W2, b2, Wg, bg)
+        ctx.meta = (kind, B, N, Cn, r)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        kind, B, N, Cn, r = ctx.meta
+        npar = 18 if kind == _lib.SE_DASE else 4
+        if g is None:
+            return (None,) * (2 + npar)
+        x, save, W1, b1, W2, b2, Wg, bg = ctx.saved_tensors
+        g = _c(g)
+        need = ctx.needs_input_grad
+        want = [False] * 6          # dW1, db1, dW2, db2, dWg, dbg
+        if not _dgrad_only:
+            if kind == _lib.SE_DASE:
+                want[4], want[5] = need[2], need[3]
+                for i in range(4):
+                    want[i] = any(need[4 + 4 * k + i] for k in range(4))
+            else:
+                want[:4] = need[2:6]
+        dx = _empty_like(x) if need[0] else None
+        grads = [_empty_like(t) if w else None for w, t in zip(want, (W1, b1, W2, b2, Wg, bg))]
+        d = _se_desc(kind, B, N, Cn, r, W1, b1, W2, b2, Wg, bg)
+        _, ws_b = _se_sizes(d)
+        ws = torch.empty((ws_b // 4,), device=x.device, dtype=torch.float32)
+        call("mdvit_se_adapter_bwd", C.byref(d), _p(g), _p(x), _p(save), _p(dx), *[_p(t) for t in grads], _p(ws), ws_b, _stream())
+        if kind == _lib.SE_USE:
+            return (dx, None) + tuple(t if n else None for t, n in zip(grads[:4], need[2:6]))
+        out = [dx, None, grads[4] if need[2] else None, grads[5] if need[3] else None]
+        for k in range(4):
+            for i in range(4):
+                out.append(grads[i][k] if (grads[i] is not None and need[4 + 4 * k + i]) else None)
+        return tuple(out)
+
+
+def se_adapter(x, kind, params):
+    """The squeeze-excite adapter on tokens x [B, N, C] (any [B, ..., C] is taken as tokens): kind "dase" | "use"; params as _SeAdapter lists them."""
+    k = SE_KINDS[kind] if isinstance(kind, str) else int(kind)
+    shp = x.shape
+    y = _SeAdapter.apply(_c(x).view(shp[0], -1, shp[-1]), k, *params)
+    return y.view(shp)
+
+
+# ------------------------------------------------------------------------------------------------
 # Domain adapter + factorized attention core
 # ------------------------------------------------------------------------------------------------
 _da_pre = None          # inside da_precomputed(): {W2.data_ptr(): a [B, C]} for the label batch of the forward in progress

@@ -299,8 +299,10 @@ def _fuse_batches(batches, fuse_domains, num_domains, use_domain_label):
 
 def base_train_step(model, batches: Sequence[tuple], optimizer=None, reducer: Optional[GradBucketReducer] = None,
                     num_domains: int = 4, use_domain_label: bool = False,
-                    accumulator: Optional[GradAccumulator] = None) -> Dict[str, torch.Tensor]:
-    """multi_train_BASE.py:150-200: per domain loss = BCE + Dice, one backward of the sum."""
+                    accumulator: Optional[GradAccumulator] = None, fuse_domains: int = 1) -> Dict[str, torch.Tensor]:
+    """multi_train_BASE.py:150-200: per domain loss = BCE + Dice, one backward of the sum.
+    fuse_domains > 1 (models whose forward takes `groups`: BASE_DASE / BASE_USE): runs of up to that many equally shaped domain batches go through ONE
+    forward, model(img, groups=G) -- BatchNorm statistics per domain batch, the losses per domain batch and summed: the same step as one forward per domain."""
     ops.refresh_transposes()          # cached W^T / weight planes follow the last optimizer update (one launch each)
     if accumulator is not None:
         accumulator.zero()
@@ -311,12 +313,24 @@ def base_train_step(model, batches: Sequence[tuple], optimizer=None, reducer: Op
     else:
         model.zero_grad(set_to_none=True)
     tot = None
+    if fuse_domains > 1:
+        if use_domain_label:
+            raise ValueError("base_train_step: fuse_domains is for the models that take no domain label")
+        batches = _fuse_batches(batches, fuse_domains, num_domains, False)
     for i, (img, label, set_id, *pre) in enumerate(batches):          # pre[0]: the one-hot domain label already on the device (graph capture)
+        G = pre[1] if len(pre) > 1 else 1                             # domain batches fused into this forward (see _fuse_batches)
         if use_domain_label:
             out = model(img, pre[0] if pre and pre[0] is not None else F.one_hot(set_id.cpu(), num_domains).float().to(img.device, non_blocking=True))
+        elif G > 1:
+            out = model(img, groups=G)
         else:
             out = model(img)
-        l = seg_loss(out, label)
+        if G > 1:
+            Bd = img.shape[0] // G
+            og = ops.split_groups(out, G)
+            l = functools.reduce(operator.add, [seg_loss(og[g], label[g * Bd:(g + 1) * Bd]) for g in range(G)])
+        else:
+            l = seg_loss(out, label)
         last = i == len(batches) - 1
         if accumulator is not None:
             accumulator.begin_sweep(last)
