@@ -572,7 +572,9 @@ int mdvit_da_bwd(const float* label, const float* W1, const float* b1, const flo
  * with M = softmax_over_tokens(k)^T v.  crpe weights: [s3*Ch,1,3,3], [s5*Ch,1,5,5], [s7*Ch,1,7,7] (+bias).
  * a == NULL: no domain adapter (mpvit.py:347-373).  kmax/ksum [B,C] and Mmat [B,C,Ch] are saved for backward.
  * Backward returns dqkv, the crpe gradients (all six may be NULL: dgrad only) and e = a * dL/da (NULL when a is NULL).  dqkv == NULL: e alone (one pass over dout and out) --
- * what the data-gradient-only sweep needs at the first adapter of the network.
+ * what the data-gradient-only sweep needs at the first adapter of the network.  The full backward is bit-repeatable from call to call in everything it returns
+ * (tests/test_gpu_attention.py); the e of the dqkv == NULL call is NOT: its kernel adds the threads' sums with floating-point atomics in LDS, in arrival order, so e
+ * may differ in the last bits between two identical calls.
  * Built (C, heads): (64, 8) and (128, 8) -- head dim 8 / 16 -- and head dim 40 / 64 with C <= 512 (MDViT: (320, 8), (512, 8)); mdvit_factoratt_fwd / _bwd answer
  * MDVIT_E_SHAPE for anything else, before any launch. */
 size_t mdvit_factoratt_ws_bytes(int32_t B, int32_t N, int32_t C, int32_t heads);

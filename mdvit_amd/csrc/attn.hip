@@ -55,7 +55,6 @@ __global__ __launch_bounds__(256) void fa_partial_kernel(const float* __restrict
     float* s_m = sm + (STAGE > RED ? STAGE : RED);     // running column max
     float* s_s = s_m + NB * 32;                        // running column exp-sum
     float* s_f = s_s + NB * 32;                        // this tile's rescale factor exp(m_old - m_new)
-    float* s_e = s_s;                                  // !SOFTMAX: the workgroup's e sums (the softmax state is not used then)
     float* s_pm = s_f + NB * 32;                       // SOFTMAX: [256 / GW token phases][GW] column maxima of the tile, and
     float* s_ps = s_pm + 256;                          //          the running exp-sums per phase
     const int stile = blockIdx.x, c0 = blockIdx.y * GW, b = blockIdx.z;
@@ -70,7 +69,6 @@ __global__ __launch_bounds__(256) void fa_partial_kernel(const float* __restrict
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     if (SOFTMAX && threadIdx.x < NB * 32) { s_m[threadIdx.x] = -INFINITY; s_s[threadIdx.x] = 0.f; s_f[threadIdx.x] = 1.f; }
     if (SOFTMAX) s_ps[threadIdx.x] = 0.f;
-    if (!SOFTMAX && e_part && threadIdx.x < NB * 32) s_e[threadIdx.x] = 0.f;
     constexpr int NVE = (FA_T * GQ + 255) / 256;
     float4 eacc[(!SOFTMAX) ? NVE : 1];                  // e sums of this thread's staging slots (slot v always carries channel quad (tid + 256 v) % GQ)
 #pragma unroll
@@ -195,18 +193,22 @@ __global__ __launch_bounds__(256) void fa_partial_kernel(const float* __restrict
         for (int j = 0; j < 256 / GW; ++j) ssum += s_ps[j * GW + threadIdx.x];
         ws_m[o] = s_m[threadIdx.x]; ws_s[o] = ssum;
     }
-    if (!SOFTMAX && e_part) {                          // (the loop ended with a barrier; s_e was cleared before it)
+    if (!SOFTMAX && e_part) {                          // (the loop ended with a barrier: the operand tile xs is dead and takes the threads' e sums, slot for slot)
+        // The sums of the FA_T token slots of a column are added in slot order by ONE thread.  (Before: float atomicAdd into LDS, whose order is the order the
+        // waves arrive in -- e, and dW1 .. db2 behind it, differed in the last bits from one call to the next.)
 #pragma unroll
         for (int v = 0; v < NVE; ++v) {
-            const int i = threadIdx.x + 256 * v, q = i % GQ;
-            if (i < FA_T * GQ) {
-                atomicAdd(&s_e[4 * q + 0], eacc[v].x); atomicAdd(&s_e[4 * q + 1], eacc[v].y);
-                atomicAdd(&s_e[4 * q + 2], eacc[v].z); atomicAdd(&s_e[4 * q + 3], eacc[v].w);
-            }
+            const int i = threadIdx.x + 256 * v, n = i / GQ, q = i % GQ;
+            if (i < FA_T * GQ) *reinterpret_cast<float4*>(xs + n * GW + 4 * q) = eacc[v];
         }
         __syncthreads();
-        if (threadIdx.x < GW) e_part[((long)b * NTS + stile) * g.C + c0 + threadIdx.x] = s_e[threadIdx.x];
-        __syncthreads();                               // (s_e aliases nothing the reduction below touches, but keep the phases apart)
+        if (threadIdx.x < GW) {
+            float e4[4] = {0.f, 0.f, 0.f, 0.f};        // four independent chains, folded in a fixed order
+#pragma unroll
+            for (int n = 0; n < FA_T; ++n) e4[n & 3] += xs[n * GW + threadIdx.x];
+            e_part[((long)b * NTS + stile) * g.C + c0 + threadIdx.x] = (e4[0] + e4[1]) + (e4[2] + e4[3]);
+        }
+        __syncthreads();                               // (the reduction below reuses the staging area)
     }
     constexpr int RW = NB * 32;            // padded row width of a partial result
     float* red = sm + wave * RW * RW;
@@ -1045,6 +1047,8 @@ size_t fa_ws_floats(int B, int N, int C, int heads) {
 // 64-token tiles a workgroup of the partial kernels walks.  A function of the IMAGE's token count alone -- never of the batch: an image's arithmetic (which
 // tiles meet in which partial row, in which order) must not depend on how many images share the launch, or the domain-batched forward stops being the
 // per-domain forwards bit for bit (tests/test_gpu_model.py: test_bench_step_fused_forward_equals_per_domain_at_512).
+// (tests/test_gpu_attention.py restates this function, the combine choice below and the tiles-per-workgroup loop of mdvit_factoratt_bwd in `reached()` to state which
+// code each of its shapes runs: change them together.)
 int fa_nsub(int NT) { return NT >= 128 ? 8 : (NT >= 64 ? 4 : (NT >= 16 ? 2 : 1)); }
 
 // The (C, heads) combinations the kernels are built for: 8 heads at C = 64 / 128 (Ch = 8 / 16: the streaming kernels are compiled for C == 8 Ch), and one head per
@@ -1099,7 +1103,7 @@ extern "C" int mdvit_factoratt_fwd(const float* qkv, const float* w3, const floa
     }
 #undef FA_PART_STREAM
 #undef FA_PART_TILES
-    if (NT > 8)
+    if (NT > 8)                            // (restated in tests/test_gpu_attention.py: reached())
         hipLaunchKernelGGL((fa_combine_softmax_kernel<32>), dim3(cdiv((long)C * g.Ch, 8), B), dim3(256), 0, s, ws_m, ws_s, ws_P, kmax, ksum, Mmat, g, NT);
     else if (NT > 2)
         hipLaunchKernelGGL((fa_combine_softmax_kernel<4>), dim3(cdiv((long)C * g.Ch, 64), B), dim3(256), 0, s, ws_m, ws_s, ws_P, kmax, ksum, Mmat, g, NT);
@@ -1205,7 +1209,7 @@ extern "C" int mdvit_factoratt_bwd(const float* dout, const float* qkv, const fl
         // 8 tiles per workgroup (4 per wave slot) amortise the staging of the two Ch x Ch matrices; fewer only while the grid would not reach one workgroup per CU
         // (measured at 32 images, C = 320 / 512: 2 tiles 227 / 157 us, 4: 163 / 97, 8: 144 / 71, 32: 140 / 71)
         const int ntiles = cdiv(g.N, 32);
-        int tpb = 8;
+        int tpb = 8;                       // (restated in tests/test_gpu_attention.py: reached())
         while (tpb > 2 && (long)cdiv(ntiles, tpb) * heads * B < 256) tpb /= 2;
         const int gx = cdiv(ntiles, tpb);
         const long nwg = (long)gx * heads * B;

@@ -1191,8 +1191,9 @@ def test_domain_adapter_forward_and_exact_gather(C):
         assert torch.equal(a_onehot, a_gather), f"domain {d}: gather not bit-exact"
 
 
-def _attn_ref(qkv, crpe, a, H, W, heads):
-    """double-precision restatement of the attention core on (B,N,3C) qkv (mdvit.py:293-304)."""
+def _attn_ref(qkv, crpe, a, H, W, heads, splits=(2, 3, 3)):
+    """restatement of the attention core on (B,N,3C) qkv (mdvit.py:293-304) in the dtype of its arguments (the tests pass doubles); splits = the head counts
+    (s3, s5, s7) of the three window classes."""
     B, N, C3 = qkv.shape
     C = C3 // 3
     Ch = C // heads
@@ -1201,7 +1202,7 @@ def _attn_ref(qkv, crpe, a, H, W, heads):
     fa = q @ M
     vimg = v.permute(0, 1, 3, 2).reshape(B, C, H, W)
     w3, b3, w5, b5, w7, b7 = crpe
-    c1, c2 = 2 * Ch, 5 * Ch
+    c1, c2 = splits[0] * Ch, (splits[0] + splits[1]) * Ch
     conv = torch.cat([F.conv2d(vimg[:, :c1], w3, b3, 1, 1, 1, c1), F.conv2d(vimg[:, c1:c2], w5, b5, 1, 2, 1, c2 - c1),
                       F.conv2d(vimg[:, c2:], w7, b7, 1, 3, 1, C - c2)], 1)
     conv = conv.reshape(B, heads, Ch, N).permute(0, 1, 3, 2)
