@@ -629,6 +629,20 @@ int mdvit_seg_metrics(const float* out, const float* aux, const float* label, ui
 /* uint8 HWC image [B,H,W,3] -> fp32 CHW [B,3,H,W]:  ((float)(u8 / 255.0) - mean[c]) / std[c]  with the ImageNet mean / std
  * (create_dataset.py:25-26 norm01, :143-144,165-172 permute + transforms.Normalize), bit-exact with that sequence. */
 int mdvit_image_normalize_u8(const uint8_t* img_nhwc, float* out_nchw, int32_t B, int32_t H, int32_t W, void* stream);
+/* The loader's train augmentations (create_dataset.py:131-139,159-172: GaussNoise, HorizontalFlip, VerticalFlip, ShiftScaleRotate,
+ * RandomBrightnessContrast, then norm01 + Normalize) applied in one gather pass; Resize is taken as done (input and output sizes are equal).
+ * img [B,H,W,3] uint8, mask [B,H,W] uint8 -> out [B,3,H,W] fp32 normalised, label [B,1,H,W] fp32 in {0, 1}.  mask and label are both NULL or both set.
+ * params [B][9] = (m00 m01 m02 m10 m11 m12 alpha beta sigma): the dst -> src affine map (bilinear for the image, nearest for the mask, both through
+ * BORDER_REFLECT_101), contrast gain, brightness offset in levels, noise standard deviation in levels (0: no noise).  keys [B][2]: the noise key;
+ * the noise is a pure function of (key, source element), so a launch is reproducible and a flip moves the noise with the pixels.  With the table
+ * (1 0 0 0 1 0 1 0 0) the image output is mdvit_image_normalize_u8's bit for bit.  Every address is formed from reflected and clamped taps: no
+ * table, finite or not, reads out of bounds.  B <= 65535, H*W*3 < 2^31.  The tables are drawn on the host (mdvit_amd/augment.py). */
+int mdvit_augment_normalize_u8(const uint8_t* img_nhwc, const uint8_t* mask, const float* params, const uint32_t* keys, float* out_nchw, float* label,
+                               int32_t B, int32_t H, int32_t W, void* stream);
+/* Host only, no GPU: the taps mdvit_augment_normalize_u8 (create_dataset.py:131-139,159-172, ShiftScaleRotate's sampling) uses for the source
+ * coordinate (xs, ys) of an H x W image, from the same inline code the kernel compiles.  idx5: linear indices y*W + x of the taps (y0,x0) (y0,x1)
+ * (y1,x0) (y1,x1) and of the nearest tap; w4: the four bilinear weights.  Non-finite coordinates give tap 0 with weight 1. */
+int mdvit_augment_probe_taps(float xs, float ys, int32_t H, int32_t W, int32_t* idx5, float* w4);
 
 /* ---- AdamW over all parameters in one launch (optim.AdamW, multi_train_MDViT.py:91-93) --------------------
  * table_dev: device array [n_tensors][5] of int64 {param, grad, exp_avg, exp_avg_sq (pointers), numel}; every row gets blocks_per_tensor

@@ -234,6 +234,8 @@ _SIGS = {
     "mdvit_adamw_step": [vp, i32, i32, vp, vp, f32, f32, f32, f32, i32, vp],
     "mdvit_seg_metrics": [vp, vp, vp, vp, vp, i64, vp],
     "mdvit_image_normalize_u8": [vp, vp, i32, i32, i32, vp],
+    "mdvit_augment_normalize_u8": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "mdvit_augment_probe_taps": [f32, f32, i32, i32, C.POINTER(i32), C.POINTER(f32)],
     "mdvit_seg_losses_sums": [vp, vp, vp, vp, i64, vp],
     "mdvit_seg_losses_final": [vp, vp, i64, i32, vp],
     "mdvit_seg_losses_bwd": [vp, vp, vp, vp, vp, vp, vp, i64, f32, vp],

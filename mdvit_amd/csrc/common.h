@@ -130,6 +130,15 @@ __device__ __forceinline__ float4 mdvit_drop_scale4(uint32_t k0, uint32_t k1, ui
                        __builtin_rotateright32(h, 24) >= thresh ? inv_keep : 0.0f);
 }
 
+// ---- loader arithmetic: one uint8 level of channel c -> ImageNet-normalised fp32 (create_dataset.py:25-26,143-144,165-172) ----
+// norm01 divides in float64 and the result is cast to float32; Normalize then subtracts the mean and divides by the std in fp32.
+// Shared by image_normalize_u8_kernel (loss.hip) and the augmentation kernel (augment.hip): the two agree bit for bit.
+__device__ __forceinline__ float mdvit_normalize_level(unsigned char level, int c) {
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    const float v = (float)((double)level / 255.0);
+    return (v - mean[c]) / stdv[c];
+}
+
 // Workgroup ids go round robin over the 8 XCDs (each with its own L2): consecutive LOGICAL ids on ONE XCD, bijectively.  For kernels whose neighbouring
 // workgroups re-read the same lines (bilinear taps, row folds): with the raw id every XCD fetches them from HBM once more.
 __device__ __forceinline__ unsigned mdvit_xcd_logical_block() {

@@ -141,17 +141,13 @@ __global__ void seg_metric_final_kernel(const unsigned long long* __restrict__ c
 }
 
 // ---- input pipeline: uint8 HWC image -> ImageNet-normalised fp32 CHW (create_dataset.py:25-26,143-144,165-172) --------
-// norm01 divides in float64 and the result is cast to float32; Normalize then subtracts the mean and divides by the std in fp32
+// the arithmetic is mdvit_normalize_level (common.h), shared with the augmentation kernel
 __global__ __launch_bounds__(256) void image_normalize_u8_kernel(const unsigned char* __restrict__ img, float* __restrict__ out, int B, int H, int W) {
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     const long npix = (long)B * H * W;
     for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long)gridDim.x * blockDim.x) {
         const long b = p / ((long)H * W), hw = p % ((long)H * W);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v = (float)((double)img[p * 3 + c] / 255.0);
-            out[(b * 3 + c) * (long)H * W + hw] = (v - mean[c]) / stdv[c];
-        }
+        for (int c = 0; c < 3; ++c) out[(b * 3 + c) * (long)H * W + hw] = mdvit_normalize_level(img[p * 3 + c], c);
     }
 }
 }  // namespace

@@ -3120,6 +3120,28 @@ def image_normalize_u8(img_u8_nhwc):
     return y
 
 
+def augment_normalize_u8(img_u8_nhwc, mask_u8, params, keys):
+    """uint8 [B,H,W,3] (+ uint8 mask [B,H,W] or None) on the device, params f32 [B,9] and keys int32 [B,2] (mdvit_amd.augment.draw_train_aug) ->
+    (ImageNet-normalised fp32 [B,3,H,W], fp32 label [B,1,H,W] or None): the loader's train augmentations (create_dataset.py:131-139,159-172) and its
+    norm01 + permute + Normalize as one gather kernel.  With the identity table the image is image_normalize_u8's bit for bit."""
+    if img_u8_nhwc.dtype != torch.uint8 or img_u8_nhwc.dim() != 4 or img_u8_nhwc.shape[-1] != 3 or not img_u8_nhwc.is_cuda:
+        raise _lib.MdvitHipError("augment_normalize_u8 expects a CUDA uint8 tensor [B,H,W,3]")
+    x = _c(img_u8_nhwc)
+    B, H, W_, _ = x.shape
+    if mask_u8 is not None and (mask_u8.dtype != torch.uint8 or tuple(mask_u8.shape) != (B, H, W_) or mask_u8.device != x.device):
+        raise _lib.MdvitHipError(f"augment_normalize_u8 expects the mask as a uint8 tensor [{B},{H},{W_}] on the image's device")
+    if params.dtype != torch.float32 or tuple(params.shape) != (B, 9) or params.device != x.device:
+        raise _lib.MdvitHipError(f"augment_normalize_u8 expects params as an fp32 tensor [{B},9] on the image's device")
+    if keys.dtype != torch.int32 or tuple(keys.shape) != (B, 2) or keys.device != x.device:
+        raise _lib.MdvitHipError(f"augment_normalize_u8 expects keys as an int32 tensor [{B},2] on the image's device")
+    m = None if mask_u8 is None else _c(mask_u8)
+    params, keys = _c(params), _c(keys)
+    y = torch.empty((B, 3, H, W_), device=x.device, dtype=torch.float32)
+    lab = None if m is None else torch.empty((B, 1, H, W_), device=x.device, dtype=torch.float32)
+    call("mdvit_augment_normalize_u8", _p(x), _p(m), _p(params), _p(keys), _p(y), _p(lab), B, H, W_, _stream())
+    return y, lab
+
+
 # ------------------------------------------------------------------------------------------------
 # a whole backward sweep on a stream of its own
 # ------------------------------------------------------------------------------------------------
