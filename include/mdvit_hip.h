@@ -522,10 +522,14 @@ size_t mdvit_upsample_bwd_ws_bytes(int32_t B, int32_t Hi, int32_t Wi, int32_t Ho
 /* adjoint, separable: dy [B,Ho,Wo,C] -> (width pass) ws [B,Ho,Wi,C] -> (height pass) dx [B,Hi,Wi,C] */
 int mdvit_upsample_bwd(const float* dy, float* dx, void* ws, size_t ws_bytes, int32_t B, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
                        int32_t C, void* stream);
+/* A/B and test hook for both adjoints (mdvit_upsample_bwd, mdvit_upsample_multi_bwd): 1 (default) = ONE kernel where the shape allows it -- every factor an even
+ * integer up to 16; the single-source call for C <= 4 (the logit resizes), the multi-source call for C % 32 == 0, sum_i Wi_i <= 128 and two staged dy row slices plus the weight tables within 64 KB of LDS (Wo <= 224 with three sources: the peer heads) --
+ * which leaves the workspace unread and gives the two passes' results bit for bit; 0 = the two passes everywhere.  The workspace sizes do not depend on it. */
+int mdvit_upsample_bwd_config(int32_t fused);
 
 /* y = base + sum_i resize(x_i) over n <= 3 NHWC sources of different sizes in ONE pass (the sum over the four encoder features in the peer heads'
  * fuse conv, Decoders.py:320-331: chained single-source calls move the [B,Ho,Wo,512] sum twice per source); base optional, may be y.  The
- * backward folds dy along W for all sources in one launch (workspace: sum_i B Ho Wi_i C floats) and along H per source.  C % 4 == 0.
+ * backward folds dy along W for all sources in one launch (workspace: sum_i B Ho Wi_i C floats) and along H per source, or both ways in one kernel (mdvit_upsample_bwd_config).  C % 4 == 0.
  * xs / dxs / Hi / Wi are HOST arrays of n entries. */
 int mdvit_upsample_multi_fwd(const float* const* xs, const int32_t* Hi, const int32_t* Wi, int32_t n, const float* base, float* y, int32_t B, int32_t Ho,
                              int32_t Wo, int32_t C, void* stream);

@@ -225,6 +225,7 @@ _SIGS = {
     "mdvit_upsample_multi_bwd": [vp, vp, vp, vp, i32, vp, C.c_size_t, i32, i32, i32, i32, vp],
     "mdvit_upsample_fwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "mdvit_upsample_bwd": [vp, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, i32, vp],
+    "mdvit_upsample_bwd_config": [i32],
     "mdvit_da_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mdvit_da_bwd": [vp] * 7 + [f32] + [vp] * 4 + [vp, C.c_size_t] + [i32] * 5 + [vp],
     "mdvit_factoratt_fwd": [vp] * 13 + [vp, C.c_size_t] + [i32] * 8 + [vp],

@@ -846,6 +846,231 @@ __global__ __launch_bounds__(256) void upsample_multi_bwd_w_lds_kernel(UpMulti p
     }
 }
 
+// The whole adjoint in ONE kernel for even integer factors: nothing of tmp size reaches HBM (the two passes above move 412 MB per peer-head call -- dy in, the three
+// [B,Ho,Wi,C] width folds out and in again, dx out -- for 178 MB of dy and dx).  Workgroup = (32-channel slice, band of UA_R dy rows, image); it walks the dy rows its dx
+// rows touch in ascending order (the band plus s / 2 halo rows on each side for a factor s), stages each row's [Wo][32] slice in LDS as the kernel above does (the next two
+// rows are in flight in registers while this one is folded: two LDS buffers, one barrier per row), and a thread keeps UA_ITEMS (source column, channel quad) items: it forms
+// tmp[o][j] with the width fold of the kernel above, in registers, and folds it at once into the two dx rows of its source that dy row o touches -- input row r is touched
+// exactly by o in [s r - s / 2, s r + 3 s / 2) (out_range), so exactly two rows are open at any o: the even one in aE, the odd one in aO.  A row is stored when its range
+// ends, by the band that owns it (s r in [R0, R0 + UA_R)); rows of the neighbouring bands are accumulated over the part of their range the walk covers and dropped.
+// Same taps, same order, same fmaf, same weight expressions as pass W followed by pass H: bit-identical.  No atomics, no cross-workgroup sums.
+// The width fold runs over the column's whole window t in [s j - s / 2, s j + 3 s / 2), 2 s taps in groups of 8 / 4 with every LDS read of a group issued before its first
+// fmaf (a loop over the clipped range [lo, hi) left each group of 4 taps waiting for LDS on its own: 63 us per peer-head call, 55 us this way); the taps a border column
+// has outside the image read a zero pad with weight 0 -- fmaf(0, 0, acc) is acc, whatever acc holds.
+constexpr int UA_R = 16;
+constexpr int UA_ITEMS = 4;
+constexpr int UA_PAD = 8;                 // zero pixels on each side of a staged dy row: the taps a column's 2 s wide window has outside the image (s / 2 <= 8) read 0, weight 0
+constexpr int UA_HT = UA_R + 32;          // dy rows a band can walk: a row's range may begin s / 2 before the band and end 3 s / 2 after it, s <= 16
+
+template <int NPF>          // float4 of a dy row slice per thread: Wo * 8 <= 256 * NPF
+__global__ __launch_bounds__(256) void upsample_multi_bwd_fused_kernel(UpMulti p, const float* __restrict__ dy, int Ho, int Wo, int C) {
+    extern __shared__ __attribute__((aligned(16))) float s_rows[];          // [2][UA_PAD + Wo + UA_PAD][32], then the two weight tables
+    const int rowf = (Wo + 2 * UA_PAD) * 32;                                // floats per staged row
+    float4* s_ht = reinterpret_cast<float4*>(s_rows + 2 * rowf);            // [UA_HT][3]: per walked dy row and source {wE, wO, event}
+    float* s_wt = reinterpret_cast<float*>(s_ht + UA_HT * 3);               // per source, per column j: the 2 s width weights of t = s j - s / 2 + u
+    const int c0 = blockIdx.x * 32, b = blockIdx.z;
+    const int R0 = blockIdx.y * UA_R, R1 = min(R0 + UA_R, Ho);
+    int ob = Ho, oe = 0;                                                    // the dy rows the band's dx rows touch: [ob, oe)
+    for (int i = 0; i < p.n; ++i) {
+        const int s = Ho / p.Hi[i];
+        const int rf = (R0 + s - 1) / s, re = min(p.Hi[i], (R1 + s - 1) / s);
+        if (rf < re) { ob = min(ob, max(0, s * rf - s / 2)); oe = max(oe, min(Ho, s * (re - 1) + 3 * s / 2)); }
+    }
+    if (ob >= oe) return;
+    // The weights do not depend on the item's channel quad or (width) on the dy row, (height) on the column: computed once per workgroup with the expressions of the two
+    // passes, read from LDS in the folds (recomputing them per tap, as the two passes do, made this kernel ALU bound: 108 us for the peer heads against 98 us in two passes).
+    // Width: s_wt[2 Wo i + 2 s j + u] for source i, column j, tap t = s j - s / 2 + u (0 outside the image).
+    // Height: with rh the source row whose range opens last at or before o (s rh <= o + s / 2), rows rh - 1 and rh are the open ones; wE / wO are the weights of the even /
+    // the odd one of them (a row that does not exist, -1 or Hi, gets 0 and is never stored); event != 0: dy row o is the last of row rd = rh - 1 -- it is stored if this band
+    // owns it (event & 1) and its sum restarts at 0 for row rd + 2: event = 2 (rd + 2) + owned.
+    for (int e = threadIdx.x; e < (oe - ob) * p.n; e += 256) {
+        const int o = ob + e / p.n, i = e % p.n;
+        const int Hi = i == 0 ? p.Hi[0] : i == 1 ? p.Hi[1] : p.Hi[2];
+        const int s = Ho / Hi, rh = (o + s / 2) / s;
+        int i0, i1; float l;
+        bilin_src(o, Hi, (float)Hi / (float)Ho, i0, i1, l);
+        const int rE = (rh & 1) ? rh - 1 : rh, rO = (rh & 1) ? rh : rh - 1;
+        const float wE = (i0 == rE ? 1.f - l : 0.f) + (i1 == rE ? l : 0.f);
+        const float wO = (i0 == rO ? 1.f - l : 0.f) + (i1 == rO ? l : 0.f);
+        int ev = 0;
+        if ((o + 1 + s / 2) % s == 0) {
+            const int rd = rh - 1, rf = (R0 + s - 1) / s, re = min(Hi, (R1 + s - 1) / s);
+            ev = 2 * (rd + 2) + (rd >= rf && rd < re ? 1 : 0);
+        }
+        s_ht[(o - ob) * 3 + i] = make_float4(wE, wO, __int_as_float(ev), 0.f);
+    }
+    {
+        int wbase = 0;
+        for (int i = 0; i < p.n; ++i) {
+            const int Wi = p.Wi[i], s = Wo / Wi;
+            const float sc = (float)Wi / (float)Wo;
+            for (int e = threadIdx.x; e < Wi * 2 * s; e += 256) {
+                const int j = e / (2 * s), t = s * j - s / 2 + e % (2 * s);
+                float wgt = 0.f;
+                if (t >= 0 && t < Wo) {
+                    int i0, i1; float l;
+                    bilin_src(t, Wi, sc, i0, i1, l);
+                    wgt = (i0 == j ? 1.f - l : 0.f) + (i1 == j ? l : 0.f);
+                }
+                s_wt[wbase + e] = wgt;
+            }
+            wbase += Wi * 2 * s;
+        }
+    }
+    for (int e = threadIdx.x; e < 2 * 2 * UA_PAD * 8; e += 256) {          // the pads of both buffers: written once
+        const int buf = e / (2 * UA_PAD * 8), r = e % (2 * UA_PAD * 8), px = r >> 3;
+        *reinterpret_cast<float4*>(s_rows + buf * rowf + (px < UA_PAD ? px : Wo + px) * 32 + 4 * (r & 7)) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const int Wsum = p.Wi[0] + (p.n > 1 ? p.Wi[1] : 0) + (p.n > 2 ? p.Wi[2] : 0);
+    const int q = threadIdx.x & 7;
+    // item state: the source, the 2 s taps of its column (from t0 = s j - s / 2, weights at s_wt[wo ..]), where its dx column starts, and the two open rows' sums
+    int it_src[UA_ITEMS], it_t0[UA_ITEMS], it_s2[UA_ITEMS], it_wo[UA_ITEMS];
+    long it_rs[UA_ITEMS];          // floats per dx row of the source
+    float* it_dx[UA_ITEMS];        // dx + the item's (image, column, channel quad)
+    float4 aE[UA_ITEMS], aO[UA_ITEMS];
+#pragma unroll
+    for (int k = 0; k < UA_ITEMS; ++k) {
+        const int e = threadIdx.x + 256 * k;
+        int j = e >> 3, sidx = 0, wbase = 0;
+        if (j >= p.Wi[0]) {
+            j -= p.Wi[0]; sidx = 1; wbase = 2 * Wo;          // Wi 2 s = 2 Wo weights per source
+            if (j >= p.Wi[1]) { j -= p.Wi[1]; sidx = 2; wbase = 4 * Wo; }
+        }
+        if (e >= Wsum * 8) { sidx = -1; j = 0; }
+        const int Hi = sidx <= 0 ? p.Hi[0] : sidx == 1 ? p.Hi[1] : p.Hi[2];          // (selects: a per-lane index into p would put it in scratch)
+        const int Wi = sidx <= 0 ? p.Wi[0] : sidx == 1 ? p.Wi[1] : p.Wi[2];
+        float* dx = sidx <= 0 ? p.d[0] : sidx == 1 ? p.d[1] : p.d[2];
+        const int s = Wo / Wi;
+        it_src[k] = sidx;
+        it_t0[k] = s * j - s / 2 + UA_PAD; it_s2[k] = 2 * s;
+        it_wo[k] = wbase + j * 2 * s;
+        it_rs[k] = (long)Wi * C;
+        it_dx[k] = dx + ((long)b * Hi * Wi + j) * C + c0 + 4 * q;
+        aE[k] = make_float4(0.f, 0.f, 0.f, 0.f); aO[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const float* src = dy + (long)b * Ho * Wo * C + c0;
+    typedef float f4v __attribute__((ext_vector_type(4)));          // (a float4 array written under a condition lands in scratch)
+    f4v pfa[NPF], pfb[NPF];          // the dy rows o + 1 and o + 2 in flight while row o is folded (2 workgroups per CU; measured alone, two rows ahead = one row ahead: the folds, not HBM, set the step)
+#pragma unroll
+    for (int u = 0; u < NPF; ++u) {
+        const int e = threadIdx.x + 256 * u;
+        if (e < Wo * 8) *reinterpret_cast<float4*>(s_rows + (UA_PAD + (e >> 3)) * 32 + 4 * (e & 7)) = *reinterpret_cast<const float4*>(src + ((long)ob * Wo + (e >> 3)) * C + 4 * (e & 7));
+    }
+    // one dy row: request row o + 2 into `ld`, fold row o from its LDS buffer, move row o + 1 (requested a step ago) from `st` into the other buffer
+    // (a macro, expanded for the two roles of the register rows: through a lambda's references the sums landed in scratch.  The request is unconditional -- past the
+    // walk's end it repeats the last row -- because the compiler counts only loads that are certain to be issued when it waits for an older one: behind a condition,
+    // every wait for row o + 1 (vmcnt) also waited for row o + 2)
+#define UA_FMA(wv, gv) acc.x = fmaf(wv, gv.x, acc.x); acc.y = fmaf(wv, gv.y, acc.y); acc.z = fmaf(wv, gv.z, acc.z); acc.w = fmaf(wv, gv.w, acc.w);
+#define UA_STEP(o, cur, ld, st) { \
+        { \
+        _Pragma("unroll") \
+            for (int u = 0; u < NPF; ++u) { \
+                const int e = min((int)threadIdx.x + 256 * u, Wo * 8 - 1); \
+                ld[u] = *reinterpret_cast<const f4v*>(src + ((long)min(o + 2, oe - 1) * Wo + (e >> 3)) * C + 4 * (e & 7)); \
+            } \
+        } \
+        const float* s_row = s_rows + cur * rowf + 4 * q; \
+        _Pragma("unroll") \
+        for (int k = 0; k < UA_ITEMS; ++k) { \
+            if (it_src[k] < 0 || (o) >= oe) continue; \
+            const float* wt = s_wt + it_wo[k]; \
+            const float* sr = s_row + it_t0[k] * 32; \
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f); \
+            int u = 0; \
+            for (; u + 8 <= it_s2[k]; u += 8) { \
+                const float4 w0 = *reinterpret_cast<const float4*>(wt + u), w1 = *reinterpret_cast<const float4*>(wt + u + 4); \
+                const float4 g0 = *reinterpret_cast<const float4*>(sr + (u + 0) * 32), g1 = *reinterpret_cast<const float4*>(sr + (u + 1) * 32); \
+                const float4 g2 = *reinterpret_cast<const float4*>(sr + (u + 2) * 32), g3 = *reinterpret_cast<const float4*>(sr + (u + 3) * 32); \
+                const float4 g4 = *reinterpret_cast<const float4*>(sr + (u + 4) * 32), g5 = *reinterpret_cast<const float4*>(sr + (u + 5) * 32); \
+                const float4 g6 = *reinterpret_cast<const float4*>(sr + (u + 6) * 32), g7 = *reinterpret_cast<const float4*>(sr + (u + 7) * 32); \
+                UA_FMA(w0.x, g0) UA_FMA(w0.y, g1) UA_FMA(w0.z, g2) UA_FMA(w0.w, g3) UA_FMA(w1.x, g4) UA_FMA(w1.y, g5) UA_FMA(w1.z, g6) UA_FMA(w1.w, g7) \
+            } \
+            if (u < it_s2[k]) { \
+                const float4 w0 = *reinterpret_cast<const float4*>(wt + u); \
+                const float4 g0 = *reinterpret_cast<const float4*>(sr + (u + 0) * 32), g1 = *reinterpret_cast<const float4*>(sr + (u + 1) * 32); \
+                const float4 g2 = *reinterpret_cast<const float4*>(sr + (u + 2) * 32), g3 = *reinterpret_cast<const float4*>(sr + (u + 3) * 32); \
+                UA_FMA(w0.x, g0) UA_FMA(w0.y, g1) UA_FMA(w0.z, g2) UA_FMA(w0.w, g3) \
+            } \
+            const float4 h = s_ht[(o - ob) * 3 + it_src[k]]; \
+            aE[k].x = fmaf(h.x, acc.x, aE[k].x); aE[k].y = fmaf(h.x, acc.y, aE[k].y); aE[k].z = fmaf(h.x, acc.z, aE[k].z); aE[k].w = fmaf(h.x, acc.w, aE[k].w); \
+            aO[k].x = fmaf(h.y, acc.x, aO[k].x); aO[k].y = fmaf(h.y, acc.y, aO[k].y); aO[k].z = fmaf(h.y, acc.z, aO[k].z); aO[k].w = fmaf(h.y, acc.w, aO[k].w); \
+            const int ev = __float_as_int(h.z); \
+            if (ev) { \
+                const int rd = (ev >> 1) - 2; \
+                float* d = it_dx[k] + rd * it_rs[k]; \
+                if (rd & 1) { if (ev & 1) *reinterpret_cast<float4*>(d) = aO[k]; aO[k] = make_float4(0.f, 0.f, 0.f, 0.f); } \
+                else        { if (ev & 1) *reinterpret_cast<float4*>(d) = aE[k]; aE[k] = make_float4(0.f, 0.f, 0.f, 0.f); } \
+            } \
+        } \
+        if (o + 1 < oe) { \
+            float* nxt = s_rows + (cur ^ 1) * rowf + UA_PAD * 32; \
+        _Pragma("unroll") \
+            for (int u = 0; u < NPF; ++u) { \
+                const int e = threadIdx.x + 256 * u; \
+                if (e < Wo * 8) *reinterpret_cast<f4v*>(nxt + (e >> 3) * 32 + 4 * (e & 7)) = st[u]; \
+            } \
+        } \
+        __syncthreads(); \
+    }
+#pragma unroll
+    for (int u = 0; u < NPF; ++u) {          // (row ob + 1; clamped to a row of the image when the walk is a single row: then never stored)
+        const int e = min((int)threadIdx.x + 256 * u, Wo * 8 - 1);
+        pfb[u] = *reinterpret_cast<const f4v*>(src + ((long)min(ob + 1, Ho - 1) * Wo + (e >> 3)) * C + 4 * (e & 7));
+    }
+    __syncthreads();
+    for (int o = ob; o < oe; o += 2) {
+        UA_STEP(o, 0, pfa, pfb)
+        UA_STEP(o + 1, 1, pfb, pfa)          // (past the walk's end when its length is odd: requests and barrier only)
+    }
+#undef UA_STEP
+#undef UA_FMA
+    // the rows still open when the walk ends (the range of the band's last row ends with it, or at the image border)
+#pragma unroll
+    for (int k = 0; k < UA_ITEMS; ++k) {
+        if (it_src[k] < 0) continue;
+        const int Hi = it_src[k] == 0 ? p.Hi[0] : it_src[k] == 1 ? p.Hi[1] : p.Hi[2];
+        const int s = Ho / Hi, rh = (oe + s / 2) / s;
+        const int rf = (R0 + s - 1) / s, re = min(Hi, (R1 + s - 1) / s);
+        const int rE = (rh & 1) ? rh - 1 : rh, rO = (rh & 1) ? rh : rh - 1;
+        if (rE >= rf && rE < re) *reinterpret_cast<float4*>(it_dx[k] + rE * it_rs[k]) = aE[k];
+        if (rO >= rf && rO < re) *reinterpret_cast<float4*>(it_dx[k] + rO * it_rs[k]) = aO[k];
+    }
+}
+
+// One source, a scalar or a single channel quad (the C = 1 logit resizes): a thread owns an input pixel and channel, folds the 2 sw columns of each of its 2 sh output
+// rows (ascending, fmaf: pass W) and folds that value into its sum with the row weight (ascending, fmaf: pass H) -- the two passes' arithmetic in one launch, no tmp.
+__global__ __launch_bounds__(256) void upsample_bwd_fused_kernel(const float* __restrict__ dy, float* __restrict__ dx, int B, int Hi, int Wi, int Ho, int Wo, int C) {
+    const float sch = (float)Hi / (float)Ho, scw = (float)Wi / (float)Wo;
+    const long total = (long)B * Hi * Wi * C;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(e % C);
+        long r = e / C;
+        const int j = (int)(r % Wi); r /= Wi;
+        const int i = (int)(r % Hi);
+        const long b = r / Hi;
+        int lo_h, hi_h, lo_w, hi_w;
+        out_range(i, Hi, Ho, lo_h, hi_h);
+        out_range(j, Wi, Wo, lo_w, hi_w);
+        float acc = 0.f;
+        for (int o = lo_h; o < hi_h; ++o) {
+            const float* base = dy + (b * Ho + o) * Wo * C + c;
+            float tw = 0.f;
+#pragma unroll 4
+            for (int t = lo_w; t < hi_w; ++t) {
+                int i0, i1; float l;
+                bilin_src(t, Wi, scw, i0, i1, l);
+                const float wgt = (i0 == j ? 1.f - l : 0.f) + (i1 == j ? l : 0.f);
+                tw = fmaf(wgt, base[(long)t * C], tw);
+            }
+            int i0, i1; float l;
+            bilin_src(o, Hi, sch, i0, i1, l);
+            const float wgt = (i0 == i ? 1.f - l : 0.f) + (i1 == i ? l : 0.f);
+            acc = fmaf(wgt, tw, acc);
+        }
+        dx[e] = acc;
+    }
+}
+
 // y = x * dropmask / (1 - p): one hash per aligned float4 (mdvit_drop_scale4), n % 4 == 0
 __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long n4, uint32_t k0, uint32_t k1,
                                                       const uint32_t* __restrict__ seed, uint32_t thresh, float inv_keep) {
@@ -1033,6 +1258,15 @@ extern "C" int mdvit_upsample_fwd(const float* x, const float* base, float* y, i
     return MDVIT_OK;
 }
 
+// 1 (default): the bilinear adjoints run as one kernel where the shape allows it; 0: the two passes everywhere (A/B and test hook: mdvit_upsample_bwd_config)
+static int g_upsample_bwd_fused = 1;
+extern "C" int mdvit_upsample_bwd_config(int32_t fused) {
+    g_upsample_bwd_fused = fused != 0;
+    return MDVIT_OK;
+}
+// n_out / n_in an even integer in 2..16
+static bool even_factor(int n_in, int n_out) { return n_out % n_in == 0 && ((n_out / n_in) & 1) == 0 && n_out / n_in <= 16; }
+
 extern "C" size_t mdvit_upsample_bwd_ws_bytes(int32_t B, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t C) {
     if (B <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0) return 0;
     return sizeof(float) * (size_t)B * Ho * Wi * C;          // tmp [B,Ho,Wi,C] between the two passes
@@ -1044,6 +1278,11 @@ extern "C" int mdvit_upsample_bwd(const float* dy, float* dx, void* ws, size_t w
     MDVIT_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0, MDVIT_E_SHAPE, "upsample_bwd: bad shape");
     MDVIT_CHECK_ARG(ws != nullptr && ws_bytes >= mdvit_upsample_bwd_ws_bytes(B, Hi, Wi, Ho, Wo, C), MDVIT_E_WORKSPACE,
                     "upsample_bwd: workspace too small (mdvit_upsample_bwd_ws_bytes)");
+    if (g_upsample_bwd_fused && C <= 4 && even_factor(Hi, Ho) && even_factor(Wi, Wo)) {          // the logit resizes: both passes in one launch, ws unread
+        hipLaunchKernelGGL(upsample_bwd_fused_kernel, dim3(ew_grid((long)B * Hi * Wi * C)), dim3(256), 0, s, dy, dx, B, Hi, Wi, Ho, Wo, C);
+        MDVIT_LAUNCH_CHECK();
+        return MDVIT_OK;
+    }
     float* tmp = (float*)ws;
     const int vec = (C & 3) == 0 && aligned16(dy) && aligned16(dx) && aligned16(tmp);
     const long cq = vec ? C / 4 : C;
@@ -1116,6 +1355,20 @@ extern "C" int mdvit_upsample_multi_bwd(const float* dy, float* const* dxs, cons
         p.Hi[i] = Hi[i]; p.Wi[i] = Wi[i]; p.d[i] = t;
         t += (size_t)B * Ho * Wi[i] * C;
         wsum += Wi[i];
+    }
+    {   // the one-kernel adjoint (ws unread): even integer factors up to 16 each way, 32-channel slices, UA_ITEMS items and at most 8 staged float4 per thread, and
+        // two dy row slices, the height table and 2 Wo width weights per source within 64 KB of LDS (Wo <= 224 for three sources)
+        const size_t lds = sizeof(float) * (2 * ((size_t)Wo + 2 * UA_PAD) * 32 + UA_HT * 3 * 4 + 2 * (size_t)Wo * n);
+        bool ok = g_upsample_bwd_fused && C % 32 == 0 && Wo <= 256 && lds <= 65536 && wsum * 8 <= 256 * UA_ITEMS && B <= 65535 && cdiv((long)Ho, (long)UA_R) <= 65535;
+        for (int i = 0; i < n && ok; ++i) ok = even_factor(Hi[i], Ho) && even_factor(Wi[i], Wo);
+        if (ok) {
+            for (int i = 0; i < n; ++i) p.d[i] = dxs[i];
+            const dim3 grid(C / 32, (unsigned)cdiv((long)Ho, (long)UA_R), B);          // x = slice: the bands of one slice, which share halo rows, sit on one XCD when C / 32 % 8 == 0
+            if (Wo <= 128) hipLaunchKernelGGL((upsample_multi_bwd_fused_kernel<4>), grid, dim3(256), lds, s, p, dy, Ho, Wo, C);
+            else           hipLaunchKernelGGL((upsample_multi_bwd_fused_kernel<8>), grid, dim3(256), lds, s, p, dy, Ho, Wo, C);
+            MDVIT_LAUNCH_CHECK();
+            return MDVIT_OK;
+        }
     }
     const long cq = C / 4;
     const int bpr = (int)cdiv((long)wsum * cq, 256L);

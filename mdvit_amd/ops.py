@@ -2276,6 +2276,11 @@ def bn_act(y, gamma, beta, running_mean, running_var, nbt, training, act, eps=1e
 # ------------------------------------------------------------------------------------------------
 # bilinear resize (align_corners=False), optionally accumulated onto a base tensor
 # ------------------------------------------------------------------------------------------------
+_upsample_bwd_fused = os.environ.get("MDVIT_UPSAMPLE_BWD_FUSED", "1") != "0"      # the bilinear adjoints (peer heads' upsample_sum, logit resizes) as one kernel, no [B,Ho,Wi,C] round trip (0: the two passes, A/B)
+if not _upsample_bwd_fused:
+    _lib.on_load(lambda lib: lib.mdvit_upsample_bwd_config(0))
+
+
 class _Upsample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, Ho, Wo, base):
@@ -2309,7 +2314,7 @@ def upsample_bilinear(x, Ho, Wo, base=None):
 
 class _UpsampleSum(torch.autograd.Function):
     """y = base + sum_i resize(x_i) for up to three NHWC sources of different sizes in ONE pass; the backward folds dy along W for all sources
-    in one launch (the dy row is read from HBM once), along H per source; base's gradient is dy itself."""
+    in one launch (the dy row is read from HBM once), along H per source -- or, for the peer heads' shapes, both ways in ONE kernel (_upsample_bwd_fused) --; base's gradient is dy itself."""
 
     @staticmethod
     def forward(ctx, base, Ho, Wo, *xs):
