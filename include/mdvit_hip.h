@@ -630,6 +630,24 @@ int mdvit_seg_losses_groups_bwd(const float* out, const float* aux, const float*
  * live instead of `.cpu().numpy()` per domain.  counts: 8 uint64 of scratch (exact integer counts: |A&Y|, |A|, |Y|,
  * |Aaux&Y|, |Aaux|); metrics: {dice, iou, aux dice, aux iou} (0 where medpy divides 0/0).  aux may be NULL. */
 int mdvit_seg_metrics(const float* out, const float* aux, const float* label, uint64_t* counts, float* metrics, int64_t n, void* stream);
+/* The validation / test pass of an epoch on the device (multi_train_MDViT.py:236-322 validate, :351-408 test; the same loops in multi_train_BASE.py and
+ * multi_train_TransFuse.py:236-260,325-345).  out / aux / label hold the G <= 16 consecutive domain batches of ONE forward, group g = images[g] *
+ * n_per_image elements (the groups may differ in size); aux may be NULL.  images / domains are HOST arrays of G entries, read before the call returns (they
+ * travel in the kernels' arguments: no copy to the device).  One pass forms per group the loss BCE(s(out),y) + Dice(s(out),y) (the expression of
+ * mdvit_seg_losses_fwd's losses[0]; :270-278) and dice / iou / aux dice / aux iou of the thresholded outputs (mdvit_seg_metrics' expressions and its 0/0 -> 0;
+ * :281-289), and adds, for the group's domain d = domains[g] (:278-291 `* batch_len`, `num_val += batch_len`):
+ *   acc    [num_domains][8] double: loss*len, dice*len, iou*len, aux dice*len, aux iou*len, images, batches, (spare), len = images[g]
+ *   counts [num_domains][5] int64:  running totals of |A&Y|, |A|, |Y|, |Aaux&Y|, |Aaux|
+ * batch_rows [G][5] (nullable): the groups' loss, dice, iou, aux dice, aux iou of THIS call.  The caller zeroes acc / counts at the start of an epoch; calls
+ * are ordered by the stream.  No atomics, every addition in a fixed order: an epoch is bit-reproducible.  ws: mdvit_eval_ws_bytes(G) bytes (0 for a G
+ * outside 1..16), partial rows of this call only. */
+size_t mdvit_eval_ws_bytes(int32_t G);
+int mdvit_eval_accumulate(const float* out, const float* aux, const float* label, const int32_t* images, const int32_t* domains, int32_t G,
+                          int64_t n_per_image, int32_t num_domains, double* acc, int64_t* counts, float* batch_rows, void* ws, size_t ws_bytes, void* stream);
+/* acc -> table [num_domains + 1][6] fp32.  Row d: loss_sum/images, dice_sum/images, iou_sum/images, aux dice, aux iou, images (multi_train_MDViT.py:296-297).
+ * Last row, what the reference logs (:311-313,404-408): the SUM of the per-domain losses, the MEANS of the four scores over the domains that saw images,
+ * the total number of images.  A domain without images has a zero row and takes no part in the means. */
+int mdvit_eval_table(const double* acc, int32_t num_domains, float* table, void* stream);
 /* uint8 HWC image [B,H,W,3] -> fp32 CHW [B,3,H,W]:  ((float)(u8 / 255.0) - mean[c]) / std[c]  with the ImageNet mean / std
  * (create_dataset.py:25-26 norm01, :143-144,165-172 permute + transforms.Normalize), bit-exact with that sequence. */
 int mdvit_image_normalize_u8(const uint8_t* img_nhwc, float* out_nchw, int32_t B, int32_t H, int32_t W, void* stream);

@@ -234,6 +234,8 @@ _SIGS = {
     "mdvit_seg_losses_fwd": [vp, vp, vp, vp, vp, i64, vp],
     "mdvit_adamw_step": [vp, i32, i32, vp, vp, f32, f32, f32, f32, i32, vp],
     "mdvit_seg_metrics": [vp, vp, vp, vp, vp, i64, vp],
+    "mdvit_eval_accumulate": [vp, vp, vp, C.POINTER(i32), C.POINTER(i32), i32, i64, i32, vp, vp, vp, vp, C.c_size_t, vp],
+    "mdvit_eval_table": [vp, i32, vp, vp],
     "mdvit_image_normalize_u8": [vp, vp, i32, i32, i32, vp],
     "mdvit_augment_normalize_u8": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "mdvit_augment_probe_taps": [f32, f32, i32, i32, C.POINTER(i32), C.POINTER(f32)],
@@ -334,6 +336,8 @@ def _attach_prototypes(lib):
     lib.mdvit_se_adapter_save_bytes.argtypes = [C.POINTER(SeAdapterDesc)]
     lib.mdvit_se_adapter_ws_bytes.restype = C.c_size_t
     lib.mdvit_se_adapter_ws_bytes.argtypes = [C.POINTER(SeAdapterDesc)]
+    lib.mdvit_eval_ws_bytes.restype = C.c_size_t
+    lib.mdvit_eval_ws_bytes.argtypes = [i32]
     for name, sig in _SIGS.items():
         try:
             fn = getattr(lib, name)

@@ -202,6 +202,14 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ---- loss arithmetic on logits, shared by the step losses / metrics (loss.hip) and the validation pass (evaluate.hip) ----
+// nn.BCELoss's term with its log clamped at -100
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float bce_term(float p, float y) {
+    const float lp = fmaxf(logf(p), -100.0f), l1p = fmaxf(logf(1.0f - p), -100.0f);
+    return -(y * lp + (1.0f - y) * l1p);
+}
+
 // erf-GELU (nn.GELU default) and its derivative.  erf by Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7, i.e. fp32
 // round-off class): erf(z) = 1 - (a1 t + .. + a5 t^5) exp(-z^2), t = 1/(1 + p z).  With z = |x|/sqrt(2) the
 // exponential exp(-x^2/2) is shared with the Gaussian pdf of the derivative: ONE v_exp + ONE v_rcp per element

@@ -5,12 +5,7 @@
 
 namespace {
 
-// sums: 0 bce_o  1 o*y  2 o*o  3 y*y  4 bce_a  5 a*y  6 a*a  7 a*o
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float bce_term(float p, float y) {
-    const float lp = fmaxf(logf(p), -100.0f), l1p = fmaxf(logf(1.0f - p), -100.0f);
-    return -(y * lp + (1.0f - y) * l1p);
-}
+// sums: 0 bce_o  1 o*y  2 o*o  3 y*y  4 bce_a  5 a*y  6 a*a  7 a*o      (sigmoid_f, bce_term: common.h)
 
 __global__ __launch_bounds__(256) void seg_losses_sums_kernel(const float* __restrict__ out, const float* __restrict__ aux,
                                                               const float* __restrict__ label, double* __restrict__ sums, long n) {

@@ -3114,6 +3114,48 @@ def seg_metrics(out, aux, label):
     return metrics, counts
 
 
+def eval_ws_bytes(G: int) -> int:
+    """bytes of eval_accumulate's workspace for G domain batches per call (a function of G alone)"""
+    return int(_lib.load().mdvit_eval_ws_bytes(int(G)))
+
+
+def eval_accumulate(out, aux, label, images, domains, acc, counts, ws, batch_rows=None):
+    """One validation / test forward's logits into the epoch state (multi_train_MDViT.py:253-291), on the device and without a sync: out / aux (or None) /
+    label hold len(images) consecutive domain batches of images[g] images each, domains[g] their domain ids (host ints).  acc [D,8] float64 and counts
+    [D,5] int64 are added to (layout: mdvit_eval_accumulate in the header); ws: a device buffer of eval_ws_bytes(G) bytes; batch_rows [G,5] fp32 (optional)
+    receives this call's per-batch loss, dice, iou, aux dice, aux iou."""
+    out, label = _c(out.detach()), _c(label.detach().float())
+    aux = None if aux is None else _c(aux.detach())
+    _chk(out, aux, label)
+    images, domains = [int(v) for v in images], [int(v) for v in domains]
+    G = len(images)
+    for name, t, dt, cols in (("acc", acc, torch.float64, 8), ("counts", counts, torch.int64, 5)):
+        if not (t.is_cuda and t.dtype == dt and t.dim() == 2 and t.shape[1] == cols and t.is_contiguous() and t.shape[0] == acc.shape[0]):
+            raise _lib.MdvitHipError(f"eval_accumulate expects {name} as a contiguous CUDA {dt} tensor [num_domains,{cols}]")
+    if len(domains) != G or G == 0 or min(images) <= 0 or out.numel() % sum(images) or label.numel() != out.numel() or (aux is not None and aux.numel() != out.numel()):
+        raise _lib.MdvitHipError(f"eval_accumulate: {out.numel()} logits, {label.numel()} labels, images {images}, domains {domains} do not fit together")
+    if not ws.is_cuda or not ws.is_contiguous():
+        raise _lib.MdvitHipError("eval_accumulate expects the workspace as a contiguous CUDA tensor")
+    if batch_rows is not None and not (batch_rows.is_cuda and batch_rows.dtype == torch.float32 and batch_rows.is_contiguous() and batch_rows.numel() >= 5 * G):
+        raise _lib.MdvitHipError(f"eval_accumulate expects batch_rows as a contiguous CUDA fp32 tensor [{G},5]")
+    call("mdvit_eval_accumulate", _p(out), _p(aux), _p(label), (C.c_int32 * G)(*images), (C.c_int32 * G)(*domains), G, out.numel() // sum(images),
+         acc.shape[0], _p(acc), _p(counts), _p(batch_rows), _p(ws), ws.numel() * ws.element_size(), _stream())
+    return batch_rows
+
+
+def eval_table(acc, table=None):
+    """the epoch state acc [D,8] -> table [D+1,6] fp32 on the device: per domain loss, dice, iou, aux dice, aux iou, images; last row the reference's
+    logged figures (sum of the losses, means of the scores over the domains that saw images, total images; multi_train_MDViT.py:296-313,404-408)"""
+    if not (acc.is_cuda and acc.dtype == torch.float64 and acc.dim() == 2 and acc.shape[1] == 8 and acc.is_contiguous()):
+        raise _lib.MdvitHipError("eval_table expects acc as a contiguous CUDA float64 tensor [num_domains,8]")
+    if table is None:
+        table = torch.empty((acc.shape[0] + 1, 6), device=acc.device, dtype=torch.float32)
+    elif not (table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (acc.shape[0] + 1, 6)):
+        raise _lib.MdvitHipError(f"eval_table expects the table as a contiguous CUDA fp32 tensor [{acc.shape[0] + 1},6]")
+    call("mdvit_eval_table", _p(acc), acc.shape[0], _p(table), _stream())
+    return table
+
+
 def image_normalize_u8(img_u8_nhwc):
     """uint8 [B,H,W,3] on the device -> ImageNet-normalised fp32 [B,3,H,W] (the loader's norm01 + permute + Normalize)."""
     if img_u8_nhwc.dtype != torch.uint8 or img_u8_nhwc.dim() != 4 or img_u8_nhwc.shape[-1] != 3 or not img_u8_nhwc.is_cuda:
