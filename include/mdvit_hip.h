@@ -321,6 +321,32 @@ int mdvit_mlp_rc_bwd(const float* gm, const float* x, const void* W1p, const flo
                      float* dW2, void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t hidden, float drop_p, uint32_t key1_0, uint32_t key1_1,
                      const uint32_t* drop_seed, int32_t accumulate, void* stream);
 size_t mdvit_mlp_rc_wgrad_ws_bytes(int32_t M, int32_t C, int32_t hidden);
+/* The fused MLP backward kernels on the UNMASKED upstream gradient g [M, C]: each forms gm = g * dropout(mask_drop_p; mask_key0 / mask_key1 / mask_seed, element index
+ * row * C + c) * rowscale[row / rows_per_scale] in registers where it loads the rows of g -- mdvit_colsum_f32's `masked` output bit for bit -- so the mask pass over
+ * [M, C] in front of them is not needed.  Everything else as the entry of the same name without _masked; with mask_drop_p == 0 and rowscale == NULL they ARE that entry.
+ * gm_out (mdvit_mlp_rc16_dgrad_masked*, optional): the masked rows [M, C] are also written once (the fc2 weight-gradient GEMM's operand); only with a mask. */
+int mdvit_mlp_rc_dgrad_masked(const float* g, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx, int32_t M, int32_t C,
+                              int32_t hidden, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, float mask_drop_p, uint32_t mask_key0,
+                              uint32_t mask_key1, const uint32_t* mask_seed, const float* rowscale, int32_t rows_per_scale, void* stream);
+int mdvit_mlp_rc16_dgrad_masked(const float* g, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* du, float* dx, float* gm_out,
+                                int32_t M, int32_t C, int32_t hidden, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, float mask_drop_p,
+                                uint32_t mask_key0, uint32_t mask_key1, const uint32_t* mask_seed, const float* rowscale, int32_t rows_per_scale, void* stream);
+int mdvit_mlp_rc16_dgrad_masked_hbf16(const float* g, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* du, float* dx,
+                                      float* gm_out, int32_t M, int32_t C, int32_t hidden, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed,
+                                      float mask_drop_p, uint32_t mask_key0, uint32_t mask_key1, const uint32_t* mask_seed, const float* rowscale,
+                                      int32_t rows_per_scale, void* stream);
+int mdvit_mlp_rc_wgrad_masked(const float* g, const float* x, const void* W1p, const float* b1, const void* W2tp, float* dW1, float* db1, float* dW2, void* ws,
+                              size_t ws_bytes, int32_t M, int32_t C, int32_t hidden, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed,
+                              float mask_drop_p, uint32_t mask_key0, uint32_t mask_key1, const uint32_t* mask_seed, const float* rowscale, int32_t rows_per_scale,
+                              int32_t accumulate, void* stream);
+int mdvit_mlp_rc_bwd_masked(const float* g, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx_parts, float* dW1, float* db1,
+                            float* dW2, void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t hidden, float drop_p, uint32_t key1_0, uint32_t key1_1,
+                            const uint32_t* drop_seed, float mask_drop_p, uint32_t mask_key0, uint32_t mask_key1, const uint32_t* mask_seed, const float* rowscale,
+                            int32_t rows_per_scale, int32_t accumulate, void* stream);
+/* A/B and test hook: 1 (default) lets mdvit_block_bwd hand the C = 64 / 128 fused MLP backward kernels the unmasked gradient and the mask (the entries above),
+ * 0 runs the mask pass in front of them (bit-identical results; MDVIT_MLP_MASK_FOLD).  Values above 1 select cases: 2 the data-gradient-only sweeps, 4 the C = 128 full
+ * sweep (gm_out), 8 the C = 64 full sweep.  Set it before mdvit_block_bwd_ws_bytes: the workspace layout follows it. */
+int mdvit_mlp_mask_config(int32_t fold);
 /* tuning hook (tools/mlp_rc_check.py): forward kernel variant -- 2: software-pipelined waves at 2 per SIMD, 3: plain waves at 3 per SIMD */
 /* Launch ledger of mdvit_gemm_f32 (measurement only, off by default; bench.py's roofline line): mdvit_gemm_ledger(1) clears and starts it, (0) stops it; while on, every
  * mdvit_gemm_f32 call -- those of mdvit_block_fwd / _bwd included -- is counted under the kernel symbol it launches (mdvit_gemm_kernel_name, main kernel) with its algorithmic

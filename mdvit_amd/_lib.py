@@ -151,6 +151,13 @@ _SIGS = {
     "mdvit_mlp_rc16_dgrad_hbf16": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp, vp],
     "mdvit_mlp_rc_wgrad": [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, f32, u32, u32, vp, i32, vp],
     "mdvit_mlp_rc_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, f32, u32, u32, vp, i32, vp],
+    # the same kernels on the unmasked upstream gradient (mask on load): ..., mask_drop_p, mask_key0, mask_key1, mask_seed, rowscale, rows_per_scale, ...
+    "mdvit_mlp_rc_dgrad_masked": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp, f32, u32, u32, vp, vp, i32, vp],
+    "mdvit_mlp_rc16_dgrad_masked": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp, f32, u32, u32, vp, vp, i32, vp],
+    "mdvit_mlp_rc16_dgrad_masked_hbf16": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp, f32, u32, u32, vp, vp, i32, vp],
+    "mdvit_mlp_rc_wgrad_masked": [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, f32, u32, u32, vp, f32, u32, u32, vp, vp, i32, i32, vp],
+    "mdvit_mlp_rc_bwd_masked": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, f32, u32, u32, vp, f32, u32, u32, vp, vp, i32, i32, vp],
+    "mdvit_mlp_mask_config": [i32],
     "mdvit_imgconv_fwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "mdvit_imgconv_wgrad": [vp, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, i32, i32, vp],
     "mdvit_maxpool3x3s2_fwd": [vp, vp, vp, i32, i32, i32, i32, vp],

@@ -298,21 +298,30 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
 
     // ---- MLP --------------------------------------------------------------------------------------------------------------------
     const bool masked = d.drop_p > 0.f || d.rowscale2 != nullptr;
-    float* gm2 = masked ? S.take(T * C) : const_cast<float*>(dy);
+    // The fused kernels of the C = 64 / 128 blocks take dy itself and mask it where they load its rows (the *_masked entries of mlp_rc.hip, mdvit_mlp_mask_config): no
+    // mask pass in front of them.  gm2 then exists only where a weight-gradient GEMM reads it (C = 128, full sweep: the data-gradient kernel writes it as gm_out).
+    const bool rc16_path = mode != MLP_RC && mlp_rc16(d) && d.fc2t_p && d.fc1t_p;
+    const int fold_case = !want_w ? MDVIT_MASK_FOLD_AUX : (mode == MLP_RC ? MDVIT_MASK_FOLD_FULL64 : MDVIT_MASK_FOLD_FULL128);
+    const bool fold = masked && (mode == MLP_RC || rc16_path) && (g_rc_mask_fold & fold_case) != 0;
+    const float m_p = fold ? d.drop_p : 0.f;                                 // the mask descriptor of the *_masked entries: empty without the fold
+    const float* m_rs = fold ? d.rowscale2 : nullptr;
+    const bool need_gm2 = masked && (!fold || (want_w && rc16_path));
+    float* gm2 = need_gm2 ? S.take(T * C) : const_cast<float*>(dy);
+    float* gm2_w = fold ? nullptr : gm2;                                     // what the mask pass writes
     float* tmp = A.take(T * C);              // dcur2, then datt, then dcur1: consecutive lifetimes on the main stream
     float* dcur2 = tmp;
     const float* dcur2_b = nullptr;          // the second partial of dcur2 (the fused MLP backward's role 1), added by the LayerNorm backward
     float* du = nullptr;
     if (mode == MLP_RC) {
-        if (masked || want_w) {
+        if ((masked && !fold) || want_w) {          // (fold, full sweep: a read-only pass for db2 = colsum(gm))
             const size_t pb = want_w ? mdvit_partials_ws_bytes(C) : 0;
             void* pw = want_w ? (defer ? S.take_bytes(pb) : A.take_bytes(pb)) : nullptr;
             if (want_w && defer) {
                 int nb = 0;
-                BLK_RUN(mdvit_colsum_parts(dy, C, masked ? gm2 : nullptr, pw, pb, M, C, d.drop_p, d.key_fc2[0], d.key_fc2[1], d.rowscale2, N_tok, seed, s, &nb));
+                BLK_RUN(mdvit_colsum_parts(dy, C, masked ? gm2_w : nullptr, pw, pb, M, C, d.drop_p, d.key_fc2[0], d.key_fc2[1], d.rowscale2, N_tok, seed, s, &nb));
                 late[n_late++] = Late{(const float*)pw, 1, nb, C, G.fc2_b, 0, nullptr};
             } else {
-                BLK_RUN(mdvit_colsum_f32(dy, C, want_w ? G.fc2_b : nullptr, masked ? gm2 : nullptr, pw, pb, M, C, d.drop_p, d.key_fc2[0], d.key_fc2[1], d.rowscale2, N_tok,
+                BLK_RUN(mdvit_colsum_f32(dy, C, want_w ? G.fc2_b : nullptr, masked ? gm2_w : nullptr, pw, pb, M, C, d.drop_p, d.key_fc2[0], d.key_fc2[1], d.rowscale2, N_tok,
                                          acc, seed, s));
             }
         }
@@ -325,22 +334,23 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
             float* parts = roles == 1 ? dcur2 : A.take((long)roles * T * C);
             const size_t wb = mdvit_mlp_rc_wgrad_ws_bytes(M, C, Hd);
             void* ww = A.take_bytes(wb);
-            BLK_RUN(mdvit_mlp_rc_bwd(gm2, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, d.fc1t_p, parts, G.fc1_w, G.fc1_b, G.fc2_w, ww, wb, M, C, Hd, d.drop_p, d.key_fc1[0],
-                                     d.key_fc1[1], seed, acc, s));
+            BLK_RUN(mdvit_mlp_rc_bwd_masked(gm2, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, d.fc1t_p, parts, G.fc1_w, G.fc1_b, G.fc2_w, ww, wb, M, C, Hd, d.drop_p, d.key_fc1[0],
+                                            d.key_fc1[1], seed, m_p, d.key_fc2[0], d.key_fc2[1], seed, m_rs, N_tok, acc, s));
             dcur2 = parts;
             dcur2_b = roles == 2 ? parts + T * C : nullptr;
         } else {
-        BLK_RUN(mdvit_mlp_rc_dgrad(gm2, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, d.fc1t_p, dcur2, M, C, Hd, d.drop_p, d.key_fc1[0], d.key_fc1[1], seed, s));
+        BLK_RUN(mdvit_mlp_rc_dgrad_masked(gm2, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, d.fc1t_p, dcur2, M, C, Hd, d.drop_p, d.key_fc1[0], d.key_fc1[1], seed, m_p, d.key_fc2[0],
+                                          d.key_fc2[1], seed, m_rs, N_tok, s));
         if (want_w) {
             const size_t wb = mdvit_mlp_rc_wgrad_ws_bytes(M, C, Hd);
             void* ww = S.take_bytes(wb);
             if (!A.dry) { const int rc = fork_side(d, st, side); if (rc != MDVIT_OK) return rc; }
-            BLK_RUN(mdvit_mlp_rc_wgrad(gm2, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, G.fc1_w, G.fc1_b, G.fc2_w, ww, wb, M, C, Hd, d.drop_p, d.key_fc1[0], d.key_fc1[1], seed,
-                                       acc, side));
+            BLK_RUN(mdvit_mlp_rc_wgrad_masked(gm2, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, G.fc1_w, G.fc1_b, G.fc2_w, ww, wb, M, C, Hd, d.drop_p, d.key_fc1[0], d.key_fc1[1],
+                                              seed, m_p, d.key_fc2[0], d.key_fc2[1], seed, m_rs, N_tok, acc, side));
         }
         }
     } else {
-        if (masked) BLK_RUN(mdvit_colsum_f32(dy, C, nullptr, gm2, nullptr, 0, M, C, d.drop_p, d.key_fc2[0], d.key_fc2[1], d.rowscale2, N_tok, 0, seed, s));
+        if (masked && !fold) BLK_RUN(mdvit_colsum_f32(dy, C, nullptr, gm2, nullptr, 0, M, C, d.drop_p, d.key_fc2[0], d.key_fc2[1], d.rowscale2, N_tok, 0, seed, s));
         MdvitGemmDesc g;
         int rc = MDVIT_OK;
         const bool hb = hbf16(d);
@@ -348,8 +358,12 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
         if (mlp_rc16(d) && d.fc2t_p && d.fc1t_p) {
             // u recomputed, du = (gm W2) * gelu'(u) * mask and dcur2 = du W1 in one kernel; du reaches HBM only for the weight gradients
             du = want_w ? S.take(hb ? (T * Hd + 1) / 2 : T * Hd) : nullptr;
-            if (hb) BLK_RUN(mdvit_mlp_rc16_dgrad_hbf16(gm2, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, d.fc1t_p, du, dcur2, M, C, Hd, d.drop_p, d.key_fc1[0], d.key_fc1[1], seed, s));
-            else BLK_RUN(mdvit_mlp_rc16_dgrad(gm2, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, d.fc1t_p, du, dcur2, M, C, Hd, d.drop_p, d.key_fc1[0], d.key_fc1[1], seed, s));
+            const float* g_in = fold ? dy : gm2;          // fold, full sweep: the kernel writes gm2 (gm_out) for the fc2 weight-gradient GEMM below
+            float* g_out = fold && want_w ? gm2 : nullptr;
+            if (hb) BLK_RUN(mdvit_mlp_rc16_dgrad_masked_hbf16(g_in, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, d.fc1t_p, du, dcur2, g_out, M, C, Hd, d.drop_p, d.key_fc1[0],
+                                                              d.key_fc1[1], seed, m_p, d.key_fc2[0], d.key_fc2[1], seed, m_rs, N_tok, s));
+            else BLK_RUN(mdvit_mlp_rc16_dgrad_masked(g_in, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, d.fc1t_p, du, dcur2, g_out, M, C, Hd, d.drop_p, d.key_fc1[0], d.key_fc1[1],
+                                                     seed, m_p, d.key_fc2[0], d.key_fc2[1], seed, m_rs, N_tok, s));
         } else {
             du = S.take(T * Hd);
             gemm_init(g, d);

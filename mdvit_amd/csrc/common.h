@@ -69,6 +69,10 @@ int mdvit_layernorm_bwd_parts(const float* dy, const float* x, const float* gamm
                               const float* rowscale, int rows_per_scale, const uint32_t* seed, hipStream_t stream, int* nblk);
 int mdvit_colsum_parts(const float* A, long lda, float* masked, void* ws, size_t ws_bytes, int M, int N, float drop_p, uint32_t key0, uint32_t key1,
                        const float* rowscale, int rows_per_scale, const uint32_t* seed, hipStream_t stream, int* nblk);
+// mdvit_mlp_mask_config (mlp_rc.hip): which MLP backward cases of the C = 64 / 128 blocks take the unmasked upstream gradient and mask it on load
+constexpr int MDVIT_MASK_FOLD_AUX = 2, MDVIT_MASK_FOLD_FULL128 = 4, MDVIT_MASK_FOLD_FULL64 = 8;
+constexpr int MDVIT_MASK_FOLD_DEFAULT = MDVIT_MASK_FOLD_AUX | MDVIT_MASK_FOLD_FULL128 | MDVIT_MASK_FOLD_FULL64;
+extern int g_rc_mask_fold;
 // the NEXT LayerNorm backward call of this thread reads its upstream gradient as dy + dy2 (norm.hip; consumed by that call)
 void mdvit_layernorm_bwd_next_dy2(const float* dy2);
 constexpr int MDVIT_MAX_PARTIAL_ROWS = 2048;        // every partial-row reduction launches at most this many workgroups

@@ -117,9 +117,40 @@ struct LnPro { const float* g; const float* b; float* mean; float* rstd; float* 
 template <int K>
 __device__ __forceinline__ void rc_ln_rows32(float4 (&a)[K / 16], float4 (&b)[K / 16], int row, int rowc, int M, int lhi, const LnPro ln);
 
+// Row-mask prologue of the backward kernels (on != 0): the gm operand is the UNMASKED upstream gradient g and the kernel forms gm = g * dropout mask * DropPath row
+// scale in registers where it loads the rows -- chan_reduce_kernel<2>'s expression in its order (norm.hip: ds = rowscale[row / rows_per_scale], times
+// mdvit_drop_scale4 of the quad when drop, v = a * ds), so the operand is bit for bit the gm of the two-pass form and the pass over [tokens, C] goes away.
+// gm_out (rc16 data gradient only): the masked rows are also written once, for the weight-gradient GEMMs of the full sweep.
+struct RcMask {
+    const float* rowscale; float* gm_out; const uint32_t* seed;
+    int on, drop, rows_per_scale; uint32_t k0, k1, thresh; float inv_keep;
+};
+__device__ __forceinline__ float4 rc_mask4(float4 a, float rsc, bool drop, uint32_t k0, uint32_t k1, uint32_t idx4, uint32_t thresh, float inv_keep) {
+    float ds[4] = {rsc, rsc, rsc, rsc};
+    if (drop) {
+        const float4 d4 = mdvit_drop_scale4(k0, k1, idx4, thresh, inv_keep);
+        ds[0] *= d4.x; ds[1] *= d4.y; ds[2] *= d4.z; ds[3] *= d4.w;
+    }
+    return make_float4(a.x * ds[0], a.y * ds[1], a.z * ds[2], a.w * ds[3]);
+}
+// the quad pairs of a lane's row: a[i] = channels STEP i + 8 sub ..+3, b[i] = ..+4 ..+7 (STEP 16: the 32-token layout, 32: the 16-token layout)
+template <int C, int STEP>
+__device__ __forceinline__ void rc_mask_rows(float4 (&a)[C / STEP], float4 (&b)[C / STEP], int rowc, int sub, const RcMask& mk) {
+    const float rsc = mk.rowscale ? mk.rowscale[rowc / mk.rows_per_scale] : 1.f;
+    uint32_t s0 = 0, s1 = 0;
+    if (mk.seed) { s0 = mk.seed[0]; s1 = mk.seed[1]; }
+    const uint32_t k0 = mk.k0 ^ s0, k1 = mk.k1 + s1;
+    const uint32_t i0 = (uint32_t)((long)rowc * C + 8 * sub);
+#pragma unroll
+    for (int i = 0; i < C / STEP; ++i) {
+        a[i] = rc_mask4(a[i], rsc, mk.drop != 0, k0, k1, i0 + STEP * i, mk.thresh, mk.inv_keep);
+        b[i] = rc_mask4(b[i], rsc, mk.drop != 0, k0, k1, i0 + STEP * i + 4, mk.thresh, mk.inv_keep);
+    }
+}
+
 template <int C, bool LNP = false>
 __device__ __forceinline__ void rc_load_rows(const float* __restrict__ src, int row, int M, int lhi, rc_bf16x8 (&hi)[C / 16], rc_bf16x8 (&lo)[C / 16],
-                                             const LnPro* ln = nullptr) {
+                                             const LnPro* ln = nullptr, const RcMask* mk = nullptr) {
     const float* p = src + (long)min(row, M - 1) * C + 8 * lhi;
     float4 a[C / 16], b[C / 16];
 #pragma unroll
@@ -128,6 +159,7 @@ __device__ __forceinline__ void rc_load_rows(const float* __restrict__ src, int 
         b[kb] = *reinterpret_cast<const float4*>(p + 16 * kb + 4);
     }
     if constexpr (LNP) rc_ln_rows32<C>(a, b, row, min(row, M - 1), M, lhi, *ln);
+    if (mk && mk->on) rc_mask_rows<C, 16>(a, b, min(row, M - 1), lhi, *mk);
 #pragma unroll
     for (int kb = 0; kb < C / 16; ++kb) {
         const float v[8] = {a[kb].x, a[kb].y, a[kb].z, a[kb].w, b[kb].x, b[kb].y, b[kb].z, b[kb].w};
@@ -268,6 +300,7 @@ struct RcArgs {
     int hbf;                // h / du are stored as bf16 (2-byte elements behind the float pointers)
     float* h;               // rc16 forward: optional [tokens, hidden] copy of drop1(gelu(u)) (the fc2 weight-gradient GEMM's operand)
     LnPro ln;               // forward kernels with the LayerNorm prologue (LNP): x is the LayerNorm's input
+    RcMask mk;              // backward kernels: gm is the unmasked upstream gradient, masked where it is loaded (mk.on)
     float* part;            // wgrad: per-workgroup partial sums
     int M, Hd, rows_per_scale;
     int drop; uint32_t k1a, k1b, k2a, k2b, thresh; float inv_keep;
@@ -689,7 +722,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     for (int i = tid; i < p.Hd / 4; i += NW * 64) reinterpret_cast<float4*>(sB1)[i] = reinterpret_cast<const float4*>(p.b1)[i];
     rc_bf16x8 xh[KB], xl[KB], gh[KB], gl[KB];
     rc_load_rows<C>(p.x, row, p.M, lhi, xh, xl);
-    rc_load_rows<C>(p.gm, row, p.M, lhi, gh, gl);
+    rc_load_rows<C>(p.gm, row, p.M, lhi, gh, gl, nullptr, &p.mk);      // (the mask's row-scale load retires with the row loads: RC_WAIT_VM(0) below)
     rc_f32x16 dxacc[CB];
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb)
@@ -913,18 +946,31 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int srow = tid >> 4, sc4 = tid & 15;
     const int soff = srow * 128 + (((sc4 >> 1) ^ rc_swz<128>(srow)) << 4) + (sc4 & 1) * 8;
     float4 rx, rg;
+    // row mask (p.mk.on): the staged quad of g is masked before the hi / lo split (store_tile); its row-scale value travels with the tile's loads
+    float rsc = 1.f;
+    uint32_t mk0 = p.mk.k0, mk1 = p.mk.k1;
+    if (p.mk.on && p.mk.seed) { mk0 ^= p.mk.seed[0]; mk1 += p.mk.seed[1]; }
     auto load_tile = [&](int t) __attribute__((always_inline)) {
         const int row = t * 32 + srow, rc = min(row, p.M - 1);
         rx = *reinterpret_cast<const float4*>(p.x + (long)rc * C + sc4 * 4);
         rg = *reinterpret_cast<const float4*>(p.gm + (long)rc * C + sc4 * 4);
+        if (p.mk.on) {
+            if (p.mk.rowscale) {
+                // rows_per_scale >= 32: one scalar division for the tile's first row, a compare per thread
+                const int r0 = min(t * 32, p.M - 1), q0 = r0 / p.mk.rows_per_scale, e0 = (q0 + 1) * p.mk.rows_per_scale;
+                const int q = p.mk.rows_per_scale >= 32 ? q0 + (rc >= e0 ? 1 : 0) : rc / p.mk.rows_per_scale;
+                rsc = p.mk.rowscale[q];
+            }
+        }
         if (row >= p.M) rg = make_float4(0.f, 0.f, 0.f, 0.f);          // rows past the end contribute nothing
     };
-    auto store_tile = [&](int buf) __attribute__((always_inline)) {
+    auto store_tile = [&](int buf, int t) __attribute__((always_inline)) {          // t: the tile load_tile fetched
         char* b = smem + buf * 4 * TP;
         uint2 hi, lo;
         mdvit_split_bf16x3(rx, hi, lo);
         *reinterpret_cast<rc_u2*>(b + soff) = rc_u2{hi.x, hi.y};
         *reinterpret_cast<rc_u2*>(b + TP + soff) = rc_u2{lo.x, lo.y};
+        if (p.mk.on) rg = rc_mask4(rg, rsc, p.mk.drop != 0, mk0, mk1, (uint32_t)((long)min(t * 32 + srow, p.M - 1) * C + sc4 * 4), p.mk.thresh, p.mk.inv_keep);
         mdvit_split_bf16x3(rg, hi, lo);
         *reinterpret_cast<rc_u2*>(b + 2 * TP + soff) = rc_u2{hi.x, hi.y};
         *reinterpret_cast<rc_u2*>(b + 3 * TP + soff) = rc_u2{lo.x, lo.y};
@@ -939,7 +985,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     if (t_beg < t_end) {
         load_tile(t_beg);
-        store_tile(0);
+        store_tile(0, t_beg);
     }
     __syncthreads();
     for (int t = t_beg; t < t_end; ++t) {
@@ -1046,7 +1092,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int tok = t * 32 + tblk * 16 + l15;    // D: lane <-> token column, registers <-> rows c = 16 cblk + 4 g4 + r
             if (tok < p.M) *reinterpret_cast<float4*>(p.dx + ((long)role * p.M + tok) * C + cblk * 16 + 4 * g4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
         }
-        if (t + 1 < t_end) store_tile(buf ^ 1);
+        if (t + 1 < t_end) store_tile(buf ^ 1, t + 1);
         __syncthreads();
     }
 
@@ -1122,7 +1168,7 @@ __device__ __forceinline__ void rc16_ln_rows128(float4 (&a)[4], float4 (&b)[4], 
 
 template <int C, bool LNP = false>
 __device__ __forceinline__ void rc16_load_rows(const float* __restrict__ src, int row, int M, int g, rc_bf16x8 (&hi)[C / 32], rc_bf16x8 (&lo)[C / 32],
-                                               const LnPro* ln = nullptr) {
+                                               const LnPro* ln = nullptr, const RcMask* mk = nullptr) {
     const float* p = src + (long)min(row, M - 1) * C + 8 * g;
     float4 a[C / 32], b[C / 32];
 #pragma unroll
@@ -1131,6 +1177,16 @@ __device__ __forceinline__ void rc16_load_rows(const float* __restrict__ src, in
         b[ks] = *reinterpret_cast<const float4*>(p + 32 * ks + 4);
     }
     if constexpr (LNP && C == 128) rc16_ln_rows128(a, b, row, min(row, M - 1), M, g, *ln);
+    if (mk && mk->on) {
+        rc_mask_rows<C, 32>(a, b, min(row, M - 1), g, *mk);
+        if (mk->gm_out && row < M) {          // (rows past M are clamped re-reads: never stored)
+#pragma unroll
+            for (int ks = 0; ks < C / 32; ++ks) {
+                *reinterpret_cast<float4*>(mk->gm_out + (long)row * C + 8 * g + 32 * ks) = a[ks];
+                *reinterpret_cast<float4*>(mk->gm_out + (long)row * C + 8 * g + 32 * ks + 4) = b[ks];
+            }
+        }
+    }
 #pragma unroll
     for (int ks = 0; ks < C / 32; ++ks) {
         const float v[8] = {a[ks].x, a[ks].y, a[ks].z, a[ks].w, b[ks].x, b[ks].y, b[ks].z, b[ks].w};
@@ -1363,7 +1419,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OC
     for (int i = tid; i < p.Hd / 4; i += NW * 64) reinterpret_cast<float4*>(sB1)[i] = reinterpret_cast<const float4*>(p.b1)[i];
     rc_bf16x8 xh[KS], xl[KS], mh[KS], ml[KS];
     rc16_load_rows<C>(p.x, row, p.M, g, xh, xl);
-    rc16_load_rows<C>(p.gm, row, p.M, g, mh, ml);
+    // (row mask: its row-scale load retires with the row loads; the gm_out stores are YOUNGER than groups 0 and 1 and older than every later group, and vector-memory
+    //  operations retire in issue order -- the counted waits below leave the PPW (+ 2) youngest operations open, so they only become stricter at t = 0)
+    rc16_load_rows<C>(p.gm, row, p.M, g, mh, ml, nullptr, &p.mk);
     rc_f32x4 dacc[CT];
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) dacc[ct] = rc_f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1589,6 +1647,21 @@ void rc_fill(RcArgs& a, int M, int Hd, float drop_p, uint32_t k10, uint32_t k11,
     a.seed = seed;
 }
 
+// the row-mask descriptor of the *_masked entries; neither dropout nor a row scale: the descriptor stays empty and the kernel is the plain one
+int rc_mask_fill(RcMask& m, const char* who, int M, int C, float drop_p, uint32_t key0, uint32_t key1, const uint32_t* seed, const float* rowscale, int rows_per_scale,
+                 float* gm_out) {
+    MDVIT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, MDVIT_E_SHAPE, "%s: mask drop_p must lie in [0, 1)", who);
+    MDVIT_CHECK_ARG(!(drop_p > 0.f) || (long)M * C < (1L << 32), MDVIT_E_SHAPE, "%s: mask index space exceeds 2^32", who);
+    MDVIT_CHECK_ARG(aligned16(gm_out), MDVIT_E_ALIGN, "%s: gm_out must be 16-byte aligned", who);
+    memset(&m, 0, sizeof(m));
+    m.on = drop_p > 0.f || rowscale != nullptr;
+    if (!m.on) return MDVIT_OK;
+    m.drop = drop_p > 0.f; m.k0 = key0; m.k1 = key1; m.seed = m.drop ? seed : nullptr;
+    m.thresh = mdvit_drop_thresh(drop_p); m.inv_keep = 1.f / (1.f - drop_p);
+    m.rowscale = rowscale; m.rows_per_scale = rows_per_scale > 0 ? rows_per_scale : 1; m.gm_out = gm_out;
+    return MDVIT_OK;
+}
+
 }  // namespace
 
 // One bf16 plane per operand in the register-chained MLP kernels (the bf16 speed mode) instead of the bf16x3 hi / lo pair: mdvit_mlp_rc_planes(1 | 2).  A process-wide
@@ -1658,8 +1731,8 @@ extern "C" int mdvit_mlp_rc_fwd(const float* x, const void* W1p, const float* b1
     return MDVIT_OK;
 }
 
-extern "C" int mdvit_mlp_rc_dgrad(const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx,
-                                  int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, void* stream) {
+static int rc_dgrad_impl(const RcMask* mk, const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx,
+                         int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, void* stream) {
     MDVIT_CHECK_ARG(C == 64, MDVIT_E_SHAPE, "mlp_rc_dgrad: built for C = 64 (got %d)", C);
     MDVIT_CHECK_ARG(M > 0 && Hd >= 64 && Hd % 64 == 0 && Hd <= 4096, MDVIT_E_SHAPE, "mlp_rc_dgrad: need M > 0, hidden %% 64 == 0, hidden <= 4096 (M=%d hidden=%d)", M, Hd);
     MDVIT_CHECK_ARG(gm && x && W1p && b1 && W2tp && W1tp && dx, MDVIT_E_SHAPE, "mlp_rc_dgrad: null operand");
@@ -1670,6 +1743,7 @@ extern "C" int mdvit_mlp_rc_dgrad(const float* gm, const float* x, const void* W
     memset(&a, 0, sizeof(a));
     a.gm = gm; a.x = x; a.W1p = (const uint16_t*)W1p; a.b1 = b1; a.W2tp = (const uint16_t*)W2tp; a.W1tp = (const uint16_t*)W1tp; a.dx = dx;
     rc_fill(a, M, Hd, drop_p, key1_0, key1_1, 0, 0, drop_seed);
+    if (mk) a.mk = *mk;
     constexpr int NW = 4;
     const int smem = 3 * 4 * (32 * 128) + 3 * 2 * (64 * 64) + Hd * 4;
     static bool flags[64] = {false};
@@ -1686,6 +1760,22 @@ extern "C" int mdvit_mlp_rc_dgrad(const float* gm, const float* x, const void* W
     else hipLaunchKernelGGL((mlp_rc_dgrad_kernel<64, NW, false>), dim3(cdiv(M, NW * 32)), dim3(NW * 64), smem, (hipStream_t)stream, a);
     MDVIT_LAUNCH_CHECK();
     return MDVIT_OK;
+}
+
+extern "C" int mdvit_mlp_rc_dgrad(const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx,
+                                  int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, void* stream) {
+    return rc_dgrad_impl(nullptr, gm, x, W1p, b1, W2tp, W1tp, dx, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, stream);
+}
+/* mdvit_mlp_rc_dgrad on the UNMASKED upstream gradient g: the kernel forms gm = g * dropout(mask_drop_p, mask keys, index row * C + c) * rowscale[row / rows_per_scale]
+ * where it loads the rows -- mdvit_colsum_f32's `masked` output bit for bit, without the pass. */
+extern "C" int mdvit_mlp_rc_dgrad_masked(const float* g, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx,
+                                         int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed,
+                                         float mask_drop_p, uint32_t mask_key0, uint32_t mask_key1, const uint32_t* mask_seed, const float* rowscale,
+                                         int32_t rows_per_scale, void* stream) {
+    RcMask mk;
+    const int rc = rc_mask_fill(mk, "mlp_rc_dgrad_masked", M, C, mask_drop_p, mask_key0, mask_key1, mask_seed, rowscale, rows_per_scale, nullptr);
+    if (rc != MDVIT_OK) return rc;
+    return rc_dgrad_impl(&mk, g, x, W1p, b1, W2tp, W1tp, dx, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, stream);
 }
 
 static int rc_wgrad_groups(int M) {
@@ -1869,7 +1959,7 @@ extern "C" int mdvit_mlp_rc_fwd_ln_hbf16(const float* x2, const float* gamma, co
 
 /* The C = 128 (and C = 64) MLP's backward data path on 16-token waves: dx = ((gm W2) * gelu'(x W1^T + b1) * mask1) W1 in one kernel; du != NULL
  * also writes the hidden-layer gradient [M, hidden] (the operand of the two weight-gradient GEMMs of the full sweep). */
-static int rc16_dgrad_impl(int hbf, const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* du, float* dx,
+static int rc16_dgrad_impl(const RcMask* mk, int hbf, const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* du, float* dx,
                                     int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, void* stream) {
     MDVIT_CHECK_ARG(C == 64 || C == 128, MDVIT_E_SHAPE, "mlp_rc16_dgrad: built for C = 64 / 128 (got %d)", C);
     MDVIT_CHECK_ARG(M > 0 && Hd >= 64 && Hd % 32 == 0 && Hd <= 4096, MDVIT_E_SHAPE, "mlp_rc16_dgrad: need M > 0, hidden %% 32 == 0, hidden <= 4096 (M=%d hidden=%d)", M, Hd);
@@ -1882,6 +1972,7 @@ static int rc16_dgrad_impl(int hbf, const float* gm, const float* x, const void*
     a.gm = gm; a.x = x; a.W1p = (const uint16_t*)W1p; a.b1 = b1; a.W2tp = (const uint16_t*)W2tp; a.W1tp = (const uint16_t*)W1tp; a.dx = dx; a.du = du;
     a.hbf = hbf && du;
     rc_fill(a, M, Hd, drop_p, key1_0, key1_1, 0, 0, drop_seed);
+    if (mk) a.mk = *mk;
     constexpr int NW = 8;
     const int wbytes = 3 * 4 * (32 * C * 2) + 3 * 2 * (C * 64);
     const int smem = wbytes + Hd * 4;
@@ -1912,12 +2003,32 @@ static int rc16_dgrad_impl(int hbf, const float* gm, const float* x, const void*
 }
 extern "C" int mdvit_mlp_rc16_dgrad(const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* du, float* dx,
                                     int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, void* stream) {
-    return rc16_dgrad_impl(0, gm, x, W1p, b1, W2tp, W1tp, du, dx, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, stream);
+    return rc16_dgrad_impl(nullptr, 0, gm, x, W1p, b1, W2tp, W1tp, du, dx, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, stream);
 }
 /* the same with du stored as bf16 */
 extern "C" int mdvit_mlp_rc16_dgrad_hbf16(const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* du, float* dx,
                                     int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, void* stream) {
-    return rc16_dgrad_impl(1, gm, x, W1p, b1, W2tp, W1tp, du, dx, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, stream);
+    return rc16_dgrad_impl(nullptr, 1, gm, x, W1p, b1, W2tp, W1tp, du, dx, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, stream);
+}
+/* The same two on the UNMASKED upstream gradient g (see mdvit_mlp_rc_dgrad_masked); gm_out != NULL also writes the masked rows [M, C] once (the fc2
+ * weight-gradient GEMM's operand in the full sweep).  gm_out is written only where the mask is not empty (mask_drop_p > 0 or a row scale). */
+extern "C" int mdvit_mlp_rc16_dgrad_masked(const float* g, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* du, float* dx,
+                                           float* gm_out, int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed,
+                                           float mask_drop_p, uint32_t mask_key0, uint32_t mask_key1, const uint32_t* mask_seed, const float* rowscale,
+                                           int32_t rows_per_scale, void* stream) {
+    RcMask mk;
+    const int rc = rc_mask_fill(mk, "mlp_rc16_dgrad_masked", M, C, mask_drop_p, mask_key0, mask_key1, mask_seed, rowscale, rows_per_scale, gm_out);
+    if (rc != MDVIT_OK) return rc;
+    return rc16_dgrad_impl(&mk, 0, g, x, W1p, b1, W2tp, W1tp, du, dx, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, stream);
+}
+extern "C" int mdvit_mlp_rc16_dgrad_masked_hbf16(const float* g, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* du, float* dx,
+                                                 float* gm_out, int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1,
+                                                 const uint32_t* drop_seed, float mask_drop_p, uint32_t mask_key0, uint32_t mask_key1, const uint32_t* mask_seed,
+                                                 const float* rowscale, int32_t rows_per_scale, void* stream) {
+    RcMask mk;
+    const int rc = rc_mask_fill(mk, "mlp_rc16_dgrad_masked_hbf16", M, C, mask_drop_p, mask_key0, mask_key1, mask_seed, rowscale, rows_per_scale, gm_out);
+    if (rc != MDVIT_OK) return rc;
+    return rc16_dgrad_impl(&mk, 1, g, x, W1p, b1, W2tp, W1tp, du, dx, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, stream);
 }
 
 /* y[M, N] = x[M, K] Wp^T (+ bias) for K = 64 / 128, N % 32 == 0; with `residual` also x dropout(key) x rowscale[row / rows_per_scale] + residual
@@ -1964,9 +2075,9 @@ extern "C" size_t mdvit_mlp_rc_wgrad_ws_bytes(int32_t M, int32_t C, int32_t Hd) 
     return sizeof(float) * (size_t)rc_wgrad_groups(M) * (2u * (size_t)Hd * C + Hd);
 }
 
-extern "C" int mdvit_mlp_rc_wgrad(const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, float* dW1, float* db1, float* dW2,
-                                  void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1,
-                                  const uint32_t* drop_seed, int32_t accumulate, void* stream) {
+static int rc_wgrad_impl(const RcMask* mk, const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, float* dW1, float* db1, float* dW2,
+                         void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1,
+                         const uint32_t* drop_seed, int32_t accumulate, void* stream) {
     MDVIT_CHECK_ARG(C == 64, MDVIT_E_SHAPE, "mlp_rc_wgrad: built for C = 64 (got %d)", C);
     MDVIT_CHECK_ARG(M > 0 && Hd >= 256 && Hd % 256 == 0, MDVIT_E_SHAPE, "mlp_rc_wgrad: need M > 0, hidden %% 256 == 0 (M=%d hidden=%d)", M, Hd);
     MDVIT_CHECK_ARG(gm && x && W1p && b1 && W2tp && dW1 && db1 && dW2, MDVIT_E_SHAPE, "mlp_rc_wgrad: null operand");
@@ -1979,6 +2090,7 @@ extern "C" int mdvit_mlp_rc_wgrad(const float* gm, const float* x, const void* W
     memset(&a, 0, sizeof(a));
     a.gm = gm; a.x = x; a.W1p = (const uint16_t*)W1p; a.b1 = b1; a.W2tp = (const uint16_t*)W2tp; a.part = (float*)ws;
     rc_fill(a, M, Hd, drop_p, key1_0, key1_1, 0, 0, drop_seed);
+    if (mk) a.mk = *mk;
     a.groups = rc_wgrad_groups(M);
     a.tiles_per_group = cdiv((M + 31) / 32, a.groups);
     const int roles = Hd / 256;
@@ -1995,12 +2107,28 @@ extern "C" int mdvit_mlp_rc_wgrad(const float* gm, const float* x, const void* W
     return MDVIT_OK;
 }
 
+extern "C" int mdvit_mlp_rc_wgrad(const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, float* dW1, float* db1, float* dW2,
+                                  void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1,
+                                  const uint32_t* drop_seed, int32_t accumulate, void* stream) {
+    return rc_wgrad_impl(nullptr, gm, x, W1p, b1, W2tp, dW1, db1, dW2, ws, ws_bytes, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, accumulate, stream);
+}
+/* on the UNMASKED upstream gradient g: every staged [32 tokens x C] tile of g is masked in registers before its hi / lo split (see mdvit_mlp_rc_dgrad_masked) */
+extern "C" int mdvit_mlp_rc_wgrad_masked(const float* g, const float* x, const void* W1p, const float* b1, const void* W2tp, float* dW1, float* db1, float* dW2,
+                                         void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1,
+                                         const uint32_t* drop_seed, float mask_drop_p, uint32_t mask_key0, uint32_t mask_key1, const uint32_t* mask_seed,
+                                         const float* rowscale, int32_t rows_per_scale, int32_t accumulate, void* stream) {
+    RcMask mk;
+    const int rc = rc_mask_fill(mk, "mlp_rc_wgrad_masked", M, C, mask_drop_p, mask_key0, mask_key1, mask_seed, rowscale, rows_per_scale, nullptr);
+    if (rc != MDVIT_OK) return rc;
+    return rc_wgrad_impl(&mk, g, x, W1p, b1, W2tp, dW1, db1, dW2, ws, ws_bytes, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, accumulate, stream);
+}
+
 /* The whole backward of the C = 64 MLP in ONE kernel + its partial-sum fold (round 5): mdvit_mlp_rc_dgrad and mdvit_mlp_rc_wgrad recompute u = x W1^T + b1, d = gm W2 and
  * the activation twice; here they are formed once and feed all three products -- dW1 = du^T x, dW2 = gm^T h (as mdvit_mlp_rc_wgrad, bit for bit) and dx = du W1.
  * dx_parts [hidden / 256][M][C]: one partial of dx per 256-wide hidden role (the consumer adds them: mdvit_layernorm_bwd's dy2, mdvit_sum_batch); hidden in {256, 512}. */
-extern "C" int mdvit_mlp_rc_bwd(const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx_parts,
-                                float* dW1, float* db1, float* dW2, void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t Hd, float drop_p,
-                                uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, int32_t accumulate, void* stream) {
+static int rc_bwd_impl(const RcMask* mk, const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx_parts,
+                       float* dW1, float* db1, float* dW2, void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t Hd, float drop_p,
+                       uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, int32_t accumulate, void* stream) {
     MDVIT_CHECK_ARG(C == 64, MDVIT_E_SHAPE, "mlp_rc_bwd: built for C = 64 (got %d)", C);
     MDVIT_CHECK_ARG(M > 0 && (Hd == 256 || Hd == 512), MDVIT_E_SHAPE, "mlp_rc_bwd: need M > 0, hidden in {256, 512} (M=%d hidden=%d)", M, Hd);
     MDVIT_CHECK_ARG(gm && x && W1p && b1 && W2tp && W1tp && dx_parts && dW1 && db1 && dW2, MDVIT_E_SHAPE, "mlp_rc_bwd: null operand");
@@ -2013,6 +2141,7 @@ extern "C" int mdvit_mlp_rc_bwd(const float* gm, const float* x, const void* W1p
     memset(&a, 0, sizeof(a));
     a.gm = gm; a.x = x; a.W1p = (const uint16_t*)W1p; a.b1 = b1; a.W2tp = (const uint16_t*)W2tp; a.W1tp = (const uint16_t*)W1tp; a.dx = dx_parts; a.part = (float*)ws;
     rc_fill(a, M, Hd, drop_p, key1_0, key1_1, 0, 0, drop_seed);
+    if (mk) a.mk = *mk;
     a.groups = rc_wgrad_groups(M);
     a.tiles_per_group = cdiv((M + 31) / 32, a.groups);
     const int roles = Hd / 256;
@@ -2034,3 +2163,27 @@ extern "C" int mdvit_mlp_rc_bwd(const float* gm, const float* x, const void* W1p
     return MDVIT_OK;
 }
 
+extern "C" int mdvit_mlp_rc_bwd(const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx_parts,
+                                float* dW1, float* db1, float* dW2, void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t Hd, float drop_p,
+                                uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, int32_t accumulate, void* stream) {
+    return rc_bwd_impl(nullptr, gm, x, W1p, b1, W2tp, W1tp, dx_parts, dW1, db1, dW2, ws, ws_bytes, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, accumulate, stream);
+}
+/* on the UNMASKED upstream gradient g (see mdvit_mlp_rc_wgrad_masked; two 256-wide hidden roles of one token range mask the same tile twice) */
+extern "C" int mdvit_mlp_rc_bwd_masked(const float* g, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx_parts,
+                                       float* dW1, float* db1, float* dW2, void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t Hd, float drop_p,
+                                       uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, float mask_drop_p, uint32_t mask_key0, uint32_t mask_key1,
+                                       const uint32_t* mask_seed, const float* rowscale, int32_t rows_per_scale, int32_t accumulate, void* stream) {
+    RcMask mk;
+    const int rc = rc_mask_fill(mk, "mlp_rc_bwd_masked", M, C, mask_drop_p, mask_key0, mask_key1, mask_seed, rowscale, rows_per_scale, nullptr);
+    if (rc != MDVIT_OK) return rc;
+    return rc_bwd_impl(&mk, g, x, W1p, b1, W2tp, W1tp, dx_parts, dW1, db1, dW2, ws, ws_bytes, M, C, Hd, drop_p, key1_0, key1_1, drop_seed, accumulate, stream);
+}
+
+// 1 (default): the block entry hands the fused MLP backward kernels of the C = 64 / 128 blocks the unmasked upstream gradient and the mask (the *_masked entries: no
+// mask pass in front of them); 0: the two-pass form (A/B and test hook: mdvit_mlp_mask_config; same bits either way)
+// Values above 1 pick the cases one by one (the timing tool): 2 the data-gradient-only sweeps, 4 the C = 128 full sweep (gm_out), 8 the C = 64 full sweep.
+int g_rc_mask_fold = MDVIT_MASK_FOLD_DEFAULT;
+extern "C" int mdvit_mlp_mask_config(int32_t fold) {
+    g_rc_mask_fold = fold == 1 ? MDVIT_MASK_FOLD_DEFAULT : (fold & (MDVIT_MASK_FOLD_AUX | MDVIT_MASK_FOLD_FULL128 | MDVIT_MASK_FOLD_FULL64));
+    return MDVIT_OK;
+}

@@ -1285,6 +1285,25 @@ _mlp_rc16 = os.environ.get("MDVIT_MLP_RC16", "1") != "0"  # C = 128: the backwar
 # run on a side stream; "0": never (A/B)
 _mlp_rc_bwd = os.environ.get("MDVIT_MLP_RC_BWD", "1")
 _lib.on_load(lambda lib: lib.mdvit_block_config({"0": 0, "1": 1}.get(_mlp_rc_bwd, 2)))          # the C-level block entry follows the same switch (applied when the library loads)
+# The fused MLP backward kernels of the C = 64 / 128 blocks mask the upstream gradient where they load it (the mdvit_mlp_rc*_masked entries): no mask pass in front of
+# them.  0: the two-pass form (A/B, bit-identical); 1 (default): every case that is kept; above 1 a case mask -- 2 the data-gradient-only sweeps, 4 the C = 128 full
+# sweep (the kernel writes gm for the weight-gradient GEMMs), 8 the C = 64 full sweep
+_MASK_FOLD_AUX, _MASK_FOLD_FULL128, _MASK_FOLD_FULL64 = 2, 4, 8
+_MASK_FOLD_DEFAULT = _MASK_FOLD_AUX | _MASK_FOLD_FULL128 | _MASK_FOLD_FULL64
+_mlp_mask_fold = _MASK_FOLD_DEFAULT
+
+
+def set_mlp_mask_fold(v: int) -> None:
+    """the operator path and the C-level block entry follow the same switch (mdvit_mlp_mask_config)"""
+    global _mlp_mask_fold
+    v = int(v)
+    _mlp_mask_fold = _MASK_FOLD_DEFAULT if v == 1 else v & (_MASK_FOLD_AUX | _MASK_FOLD_FULL128 | _MASK_FOLD_FULL64)
+    _lib.on_load(lambda lib, v=v: lib.mdvit_mlp_mask_config(v))
+
+
+_mlp_mask_fold_env = os.environ.get("MDVIT_MLP_MASK_FOLD", "1")      # the C = 64 / 128 fused MLP backward kernels mask the upstream gradient on load, no mask pass in front (0: the two passes, A/B; above 1: a case mask)
+if _mlp_mask_fold_env != "1":
+    set_mlp_mask_fold(int(_mlp_mask_fold_env))
 
 
 def _mlp_rc_ok(Cin, Hd, b1, b2, res, W1, W2, M) -> bool:
@@ -1386,12 +1405,15 @@ class _MlpResidual(torch.autograd.Function):
             # gm = g * dropmask2 * droppath scale (+ db2 = its column sums, when parameter gradients are wanted) in one pass
             masked = drop_p > 0 or rowscale is not None
             want_w = not _dgrad_only
-            gm = _empty_like(g) if masked else g
+            # fold: the kernels below take g and the mask; the pass stays only for db2 (full sweep), read-only
+            fold = masked and bool(_mlp_mask_fold & (_MASK_FOLD_FULL64 if want_w else _MASK_FOLD_AUX))
+            gm = _empty_like(g) if masked and not fold else g
+            mk = (drop_p, k2[0], k2[1], _seed_ptr() if drop_p > 0 else None, _p(rowscale), rps) if fold else (0.0, 0, 0, None, None, 1)
             if want_w and not sunk:
                 db2 = _empty((Cin,), device=dev, dtype=torch.float32)
-            if masked or want_w:
+            if (masked and not fold) or want_w:
                 wsp, wsb, _keep = _partials_ws(Cin, dev) if want_w else (None, 0, None)
-                call("mdvit_colsum_f32", _p(g), Cin, _p(sinks[3] if sunk else db2) if want_w else None, _p(gm) if masked else None, wsp, wsb, M, Cin,
+                call("mdvit_colsum_f32", _p(g), Cin, _p(sinks[3] if sunk else db2) if want_w else None, _p(gm) if masked and not fold else None, wsp, wsb, M, Cin,
                      drop_p, k2[0], k2[1], _p(rowscale), rps, int(sunk), _seed_ptr() if drop_p > 0 else None, _stream())
             W1p, W2tp, W1tp = _wplanes(W1, False, 2), _wplanes(W2, True, 2), _wplanes(W1, True, 2)
             fused = want_w and Hd in (256, 512) and (_mlp_rc_bwd == "1" or (_mlp_rc_bwd == "auto" and not (sunk and _side_stream is not None)))
@@ -1406,8 +1428,8 @@ class _MlpResidual(torch.autograd.Function):
                 else:
                     dW1, db1, dW2 = _empty_like(W1), _empty((Hd,), device=dev, dtype=torch.float32), _empty_like(W2)
                     tgt, accf = (dW1, db1, dW2), 0
-                call("mdvit_mlp_rc_bwd", _p(gm), _p(x), _p(W1p), _p(ctx.b1_ref), _p(W2tp), _p(W1tp), _p(parts), _p(tgt[0]), _p(tgt[1]), _p(tgt[2]), _p(ws), wsb,
-                     M, Cin, Hd, drop_p, k1[0], k1[1], _seed_ptr() if drop_p > 0 else None, accf, _stream())
+                call("mdvit_mlp_rc_bwd_masked", _p(gm), _p(x), _p(W1p), _p(ctx.b1_ref), _p(W2tp), _p(W1tp), _p(parts), _p(tgt[0]), _p(tgt[1]), _p(tgt[2]), _p(ws), wsb,
+                     M, Cin, Hd, drop_p, k1[0], k1[1], _seed_ptr() if drop_p > 0 else None, *mk, accf, _stream())
                 if roles == 1:
                     dx = parts[0]
                 else:
@@ -1416,29 +1438,32 @@ class _MlpResidual(torch.autograd.Function):
                 del W1p, W2tp, W1tp
                 return dx, g, dW1, db1, dW2, db2, None, None, None
             dx = _empty_like(x)
-            call("mdvit_mlp_rc_dgrad", _p(gm), _p(x), _p(W1p), _p(ctx.b1_ref), _p(W2tp), _p(W1tp), _p(dx), M, Cin, Hd,
-                 drop_p, k1[0], k1[1], _seed_ptr() if drop_p > 0 else None, _stream())
+            call("mdvit_mlp_rc_dgrad_masked", _p(gm), _p(x), _p(W1p), _p(ctx.b1_ref), _p(W2tp), _p(W1tp), _p(dx), M, Cin, Hd,
+                 drop_p, k1[0], k1[1], _seed_ptr() if drop_p > 0 else None, *mk, _stream())
             if want_w:
                 wsb = _lib.load().mdvit_mlp_rc_wgrad_ws_bytes(M, Cin, Hd)
                 if sunk:
                     with _on_side(gm, x, W1p, W2tp):
                         ws = _empty((wsb // 4,), device=dev, dtype=torch.float32)     # allocated on the side stream: freed in its order, nothing to protect
-                        call("mdvit_mlp_rc_wgrad", _p(gm), _p(x), _p(W1p), _p(ctx.b1_ref), _p(W2tp), _p(sinks[0]), _p(sinks[1]), _p(sinks[2]), _p(ws), wsb,
-                             M, Cin, Hd, drop_p, k1[0], k1[1], _seed_ptr() if drop_p > 0 else None, 1, _stream())
+                        call("mdvit_mlp_rc_wgrad_masked", _p(gm), _p(x), _p(W1p), _p(ctx.b1_ref), _p(W2tp), _p(sinks[0]), _p(sinks[1]), _p(sinks[2]), _p(ws), wsb,
+                             M, Cin, Hd, drop_p, k1[0], k1[1], _seed_ptr() if drop_p > 0 else None, *mk, 1, _stream())
                     db2 = None
                 else:
                     dW1, db1, dW2 = _empty_like(W1), _empty((Hd,), device=dev, dtype=torch.float32), _empty_like(W2)
                     ws = _empty((wsb // 4,), device=dev, dtype=torch.float32)
-                    call("mdvit_mlp_rc_wgrad", _p(gm), _p(x), _p(W1p), _p(ctx.b1_ref), _p(W2tp), _p(dW1), _p(db1), _p(dW2), _p(ws), wsb,
-                         M, Cin, Hd, drop_p, k1[0], k1[1], _seed_ptr() if drop_p > 0 else None, 0, _stream())
+                    call("mdvit_mlp_rc_wgrad_masked", _p(gm), _p(x), _p(W1p), _p(ctx.b1_ref), _p(W2tp), _p(dW1), _p(db1), _p(dW2), _p(ws), wsb,
+                         M, Cin, Hd, drop_p, k1[0], k1[1], _seed_ptr() if drop_p > 0 else None, *mk, 0, _stream())
             del W1p, W2tp, W1tp
             return dx, g, dW1, db1, dW2, db2, None, None, None
         if not _dgrad_only and not sunk:
             db2 = torch.zeros((Cin,), device=dev, dtype=torch.float32)
         # gm = g * dropmask2 * droppath scale in one pass; db2 = column sums of gm rides on the fc2 wgrad GEMM's pass over gm (colsum_a)
         masked = drop_p > 0 or rowscale is not None
-        gm = _empty_like(g) if masked else g
-        if masked:
+        # C = 128 on the 16-token kernel: it takes g and the mask, and writes gm itself where the weight-gradient GEMMs below read it (full sweep)
+        fold = (masked and u is None and _mlp_rc16_ok(Cin, Hd, ctx.b1_ref, W1, W2, M)
+                and not (_mlp_fused and _gemm_precision >= 1 and Cin == 64) and bool(_mlp_mask_fold & (_MASK_FOLD_AUX if _dgrad_only else _MASK_FOLD_FULL128)))
+        gm = _empty_like(g) if masked and not (fold and _dgrad_only) else g
+        if masked and not fold:
             call("mdvit_colsum_f32", _p(g), Cin, None, _p(gm), None, 0, M, Cin,
                  drop_p, k2[0], k2[1], _p(rowscale), rps, 0, _seed_ptr() if drop_p > 0 else None, _stream())
         # du = (gm W2) * gelu'(u) * mask1
@@ -1454,8 +1479,9 @@ class _MlpResidual(torch.autograd.Function):
             # C = 128: u recomputed, du = (gm W2) * gelu'(u) * mask1 and dx = du W1 in ONE kernel; du reaches HBM only for the weight gradients
             du = None if _dgrad_only else _empty_like(h)
             W1p, W2tp, W1tp = _wplanes(W1, False, 2), _wplanes(W2, True, 2), _wplanes(W1, True, 2)
-            call("mdvit_mlp_rc16_dgrad", _p(gm), _p(x), _p(W1p), _p(ctx.b1_ref), _p(W2tp), _p(W1tp), _p(du), _p(dx), M, Cin, Hd,
-                 drop_p, k1[0], k1[1], _seed_ptr() if drop_p > 0 else None, _stream())
+            mk = (drop_p, k2[0], k2[1], _seed_ptr() if drop_p > 0 else None, _p(rowscale), rps) if fold else (0.0, 0, 0, None, None, 1)
+            call("mdvit_mlp_rc16_dgrad_masked", _p(g if fold else gm), _p(x), _p(W1p), _p(ctx.b1_ref), _p(W2tp), _p(W1tp), _p(du), _p(dx),
+                 _p(gm) if fold and not _dgrad_only else None, M, Cin, Hd, drop_p, k1[0], k1[1], _seed_ptr() if drop_p > 0 else None, *mk, _stream())
             del W1p, W2tp, W1tp
         else:
             du = _empty_like(h)
