@@ -316,7 +316,7 @@ int mdvit_mlp_rc16_dgrad_hbf16(const float* gm, const float* x, const void* W1p,
                                int32_t M, int32_t C, int32_t Hd, float drop_p, uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, void* stream);
 /* The whole backward of the C = 64 MLP (mpvit.py:71-78 in mdvit.py:357-360) from ONE evaluation of u = x W1^T + b1, d = gm W2 and the activation: dW1, db1, dW2 as
  * mdvit_mlp_rc_wgrad (same workspace, same fold) and the data gradient dx = du W1 as one partial per 256-wide hidden role, dx_parts [hidden / 256][M][C] -- the consumer adds
- * them (mdvit_layernorm_bwd2's dy2, or mdvit_sum_batch).  hidden in {256, 512}.  W1tp: the planes of W1^T ([2][C][hidden], mdvit_mlp_rc_dgrad's). */
+ * them (the block entry's LayerNorm backward takes the second one as its dy2 argument; the binding uses mdvit_sum_batch).  hidden in {256, 512}.  W1tp: the planes of W1^T ([2][C][hidden], mdvit_mlp_rc_dgrad's). */
 int mdvit_mlp_rc_bwd(const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx_parts, float* dW1, float* db1,
                      float* dW2, void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t hidden, float drop_p, uint32_t key1_0, uint32_t key1_1,
                      const uint32_t* drop_seed, int32_t accumulate, void* stream);
@@ -436,7 +436,9 @@ size_t mdvit_block_save_bytes(const MdvitBlockDesc* d);
 size_t mdvit_block_fwd_ws_bytes(const MdvitBlockDesc* d);
 int mdvit_block_fwd(const MdvitBlockDesc* d, const float* x, float* y, void* save, size_t save_bytes, void* ws, size_t ws_bytes, void* stream);
 /* two backward workspaces: `ws` holds what only the main stream touches (free to reuse once the call has returned: stream order), `ws_side`
- * (*side_bytes) what the side stream's weight-gradient kernels read -- the caller keeps that one alive until the side stream is done */
+ * (*side_bytes) what the side stream's weight-gradient kernels read -- the caller keeps that one alive until the side stream is done.
+ * The sizes hold for every call with the same (d, g, with_side_stream), whatever x, dy and dx are (dx == NULL included); a pass never carves past the sizes it is
+ * given: short buffers are refused with MDVIT_E_WORKSPACE before anything is enqueued. */
 size_t mdvit_block_bwd_ws_bytes(const MdvitBlockDesc* d, const MdvitBlockGrads* g, int32_t with_side_stream, size_t* side_bytes);
 int mdvit_block_bwd(const MdvitBlockDesc* d, const MdvitBlockGrads* g, const MdvitBlockStreams* st, const float* x, const void* save, size_t save_bytes,
                     const float* dy, float* dx /* NULL: not wanted */, void* ws, size_t ws_bytes, void* ws_side, size_t ws_side_bytes);

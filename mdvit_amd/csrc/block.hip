@@ -10,10 +10,20 @@
 
 namespace {
 
+// One caller-owned buffer, carved front to back.  A PLANNING arena (dry) only counts: it hands out no pointer, and nothing is launched or forked while the pass's
+// main arena is one (BLK_RUN) -- the *_bytes entries are the pass itself run on planning arenas, so a real pass takes exactly what was planned for the same
+// (desc, grads, with_side_stream): no take may hang on x, dy or dx.  A real arena refuses a request past its end: the pass stops there with MDVIT_E_WORKSPACE.
+struct ArenaOverflow {};
 struct Arena {
-    char* base; size_t off, cap; bool dry;
+    const char* name; char* base; size_t cap; bool dry; size_t off;
+    static Arena plan() { return Arena{"plan", nullptr, 0, true, 0}; }
+    static Arena over(const char* name, const void* p, size_t bytes) { return Arena{name, (char*)const_cast<void*>(p), bytes, false, 0}; }
     float* take(size_t floats) {
         const size_t bytes = (floats * sizeof(float) + 255) & ~(size_t)255;
+        if (!dry && (bytes > cap || off > cap - bytes)) {
+            mdvit_set_error(MDVIT_E_WORKSPACE, "block: the %s arena is too small: %zu bytes at offset %zu of %zu (size it with the mdvit_block_*_bytes entries)", name, bytes, off, cap);
+            throw ArenaOverflow{};          // caught by the extern "C" entry: the pointer is never handed out
+        }
         float* p = dry ? nullptr : reinterpret_cast<float*>(base + off);
         off += bytes;
         return p;
@@ -37,6 +47,12 @@ inline bool mlp_rc16(const MdvitBlockDesc& d) {
 
 // "mixed" mode: h and du of the C = 128 MLP as bf16 (they exist only on the 16-token kernels' path)
 inline bool hbf16(const MdvitBlockDesc& d) { return d.store_bf16 && mlp_rc16(d); }
+// ... and its backward data path as one kernel (u recomputed): needs the transposed planes too; otherwise two GEMMs against the fp32 transposes
+inline bool rc16_bwd(const MdvitBlockDesc& d) { return mlp_rc16(d) && d.fc2t_p && d.fc1t_p; }
+// a [tokens, C] x W^T Linear of the C = 64 / 128 blocks on the streaming short-K kernel (mlp_rc.hip: mdvit_linear_rc), given the planes of its weight
+inline bool lin_rc(const MdvitBlockDesc& d, const void* planes) {
+    return d.precision == 1 && (d.C == 64 || d.C == 128) && planes != nullptr && (long)d.B * d.H * d.W >= 1024;
+}
 
 struct Saved {        // the block's saved-for-backward tensors inside the caller's `save` buffer
     float *x1, *mean1, *rstd1, *cur1, *qkv, *a, *att, *U, *kmax, *ksum, *Mmat, *x2, *mean2, *rstd2, *cur2, *h, *u, *lse;
@@ -79,12 +95,15 @@ extern "C" int mdvit_block_config(int32_t mlp_bwd_fused) {
     return MDVIT_OK;
 }
 
-#define BLK_RUN(call)                         \
-    do {                                      \
-        if (!A.dry) {                         \
-            const int rc__ = (call);          \
-            if (rc__ != MDVIT_OK) return rc__; \
-        }                                     \
+// BLK_TRY: a step that takes from an arena (it runs while planning too); BLK_RUN: a launch, a fork -- anything that touches the device -- skipped while planning
+#define BLK_TRY(call)                      \
+    do {                                   \
+        const int rc__ = (call);           \
+        if (rc__ != MDVIT_OK) return rc__; \
+    } while (0)
+#define BLK_RUN(call)             \
+    do {                          \
+        if (!A.dry) BLK_TRY(call); \
     } while (0)
 
 // An NT product of the block on the 256-wide plane kernel (gemm_ph.hip through mdvit_gemm_planes: fp32 activations split while staged, the weight as its
@@ -117,15 +136,19 @@ int gemm_planes_nt(Arena& A, const MdvitGemmDesc& g, const void* planes, hipStre
     BLK_RUN(mdvit_gemm_planes(&pd, s));
     return MDVIT_OK;
 }
-
-// C = A W^T (+ epilogue): the forward layers
-int gemm_fwd(Arena& A, MdvitGemmDesc& g, hipStream_t s, const MdvitBlockDesc* d = nullptr, const void* planes = nullptr) {
-    if (d && ph_takes(*d, planes, g.M, g.N, g.K, epi_reads_of(g))) return gemm_planes_nt(A, g, planes, s);
-    g.trans_a = 0; g.trans_b = 1; g.allow_split = 1;
-    const size_t need = mdvit_gemm_ws_bytes(&g);
+// ... and every other product on mdvit_gemm_f32, its K-split workspace out of the arena
+int gemm_run(Arena& A, MdvitGemmDesc& g, hipStream_t s) {
+    const size_t need = g.allow_split ? mdvit_gemm_ws_bytes(&g) : 0;
     g.ws = need ? A.take_bytes(need) : nullptr; g.ws_bytes = need;
     BLK_RUN(mdvit_gemm_f32(&g, s));
     return MDVIT_OK;
+}
+
+// C = A W^T (+ epilogue): the forward layers
+int gemm_fwd(Arena& A, const MdvitBlockDesc& d, MdvitGemmDesc& g, const void* planes, hipStream_t s, int allow_split = 1) {
+    if (ph_takes(d, planes, g.M, g.N, g.K, epi_reads_of(g))) return gemm_planes_nt(A, g, planes, s);
+    g.trans_a = 0; g.trans_b = 1; g.allow_split = allow_split;
+    return gemm_run(A, g, s);
 }
 
 // dx[M,K] = g[M,N] W[N,K]: NT against the cached W^T (bf16x3) or NN (fp32)  -- ops._dgrad
@@ -136,10 +159,7 @@ int gemm_dgrad(Arena& A, const MdvitBlockDesc& d, MdvitGemmDesc& g, const float*
     if (pm_split_takes(d, g, planes_t, M, K, N)) return gemm_planes_nt(A, g, planes_t, s, true);
     if (d.precision >= 1) { g.B = Wt; g.ldb = N; g.trans_a = 0; g.trans_b = 1; g.precision = 1; }
     else { g.B = W; g.ldb = K; g.trans_a = 0; g.trans_b = 0; g.precision = 0; }
-    const size_t need = g.allow_split ? mdvit_gemm_ws_bytes(&g) : 0;
-    g.ws = need ? A.take_bytes(need) : nullptr; g.ws_bytes = need;
-    BLK_RUN(mdvit_gemm_f32(&g, s));
-    return MDVIT_OK;
+    return gemm_run(A, g, s);
 }
 
 // dW[N,K] (+)= gy[M,N]^T x[M,K], db[N] += colsum(gy)  -- the TN launch of ops._Linear.backward
@@ -150,14 +170,11 @@ int gemm_wgrad(Arena& A, const MdvitBlockDesc& d, const float* gy, const float* 
     g.a_bf16 = gy_bf16; g.b_bf16 = x_bf16;
     g.A = gy; g.B = x; g.C = dW; g.M = N; g.N = K; g.K = M; g.lda = N; g.ldb = K; g.ldc = K;
     g.trans_a = 1; g.trans_b = 0; g.allow_split = 1; g.accumulate = accumulate; g.colsum_a = db;
-    const size_t need = mdvit_gemm_ws_bytes(&g);
-    g.ws = need ? A.take_bytes(need) : nullptr; g.ws_bytes = need;
-    BLK_RUN(mdvit_gemm_f32(&g, s));
-    return MDVIT_OK;
+    return gemm_run(A, g, s);
 }
 
-// everything the side stream enqueues from here on runs after what the main stream holds now
-int fork_side(const MdvitBlockDesc& d, const MdvitBlockStreams& st, hipStream_t& side) {
+// everything the side stream enqueues from here on runs after what the main stream holds now  (a device step: through BLK_RUN)
+int fork_side(const MdvitBlockStreams& st, hipStream_t& side) {
     side = (hipStream_t)st.side;
     if (side == nullptr || side == (hipStream_t)st.main) { side = (hipStream_t)st.main; return MDVIT_OK; }
     if (st.n_events <= 0 || st.events == nullptr) return mdvit_set_error(MDVIT_E_SHAPE, "block: a side stream needs events");
@@ -181,13 +198,13 @@ int block_fwd(const MdvitBlockDesc& d, const float* x, float* y, Arena& SV, Aren
     if (sdpa_kind(d)) sv.x1 = const_cast<float*>(x);
     else BLK_RUN(mdvit_dwconv3x3_fwd(x, d.cpe_w, d.cpe_b, sv.x1, B, H, W, C, 1, 1, s));
     // cur1 = LN1(x1);  qkv = cur1 Wqkv^T + b                    (mdvit.py:286-288)
-    const bool lin_rc = d.precision == 1 && (C == 64 || C == 128) && d.qkv_p && d.proj_p && M >= 1024;       // the streaming short-K Linear (mlp_rc.hip)
+    const bool rc_lin = lin_rc(d, d.qkv_p) && lin_rc(d, d.proj_p);
     static const bool ln_prologue = [] { const char* e = getenv("MDVIT_LN_PROLOGUE"); return !(e && e[0] == '0'); }();
-    if (lin_rc && ln_prologue) {
+    if (rc_lin && ln_prologue) {
         // LN1 in the qkv kernel's prologue: the rows are normalised in the registers they are multiplied from; cur1 is still written (the qkv
         // weight-gradient GEMM reads it), x1 is read once instead of twice and one launch is gone
         BLK_RUN(mdvit_linear_rc_ln(sv.x1, d.n1_g, d.n1_b, d.ln_groups, d.eps, sv.mean1, sv.rstd1, sv.cur1, d.qkv_p, 3L * C * C, d.qkv_b, sv.qkv, 3 * C, M, 3 * C, C, s));
-    } else if (lin_rc) {
+    } else if (rc_lin) {
         BLK_RUN(mdvit_layernorm_fwd(sv.x1, d.n1_g, d.n1_b, sv.cur1, sv.mean1, sv.rstd1, M, C, d.ln_groups, d.eps, s));
         BLK_RUN(mdvit_linear_rc(sv.cur1, C, d.qkv_p, 3L * C * C, d.qkv_b, sv.qkv, 3 * C, M, 3 * C, C, 0.f, 0, 0, nullptr, 1, nullptr, 0, nullptr, s));
     } else {
@@ -195,8 +212,7 @@ int block_fwd(const MdvitBlockDesc& d, const float* x, float* y, Arena& SV, Aren
         MdvitGemmDesc g;
         gemm_init(g, d);
         g.A = sv.cur1; g.B = d.qkv_w; g.C = sv.qkv; g.M = M; g.N = 3 * C; g.K = C; g.lda = C; g.ldb = C; g.ldc = 3 * C; g.bias = d.qkv_b;
-        const int rc = gemm_fwd(A, g, s, &d, d.qkv_p);
-        if (rc != MDVIT_OK) return rc;
+        BLK_TRY(gemm_fwd(A, d, g, d.qkv_p, s));
     }
     // a = softmax_heads(MLP(one_hot));  att = a * (scale * q (softmax_tokens(k)^T v) + q * crpe(v))      (mdvit.py:293-304)
     if (d.label && !d.a_pre) BLK_RUN(mdvit_da_fwd(d.label, d.da_w1, d.da_b1, d.da_w2, d.da_b2, sv.a, B, d.D, d.da_hidden, C, d.heads, s));
@@ -210,7 +226,7 @@ int block_fwd(const MdvitBlockDesc& d, const float* x, float* y, Arena& SV, Aren
                                     d.s3, d.s5, d.s7, s));
     }
     // x2 = x1 + droppath(drop(att Wproj^T + b))      (mdvit.py:310-311,353)
-    if (lin_rc) {
+    if (rc_lin) {
         BLK_RUN(mdvit_linear_rc(sv.att, C, d.proj_p, (long)C * C, d.proj_b, sv.x2, C, M, C, C, d.drop_p, d.key_proj[0], d.key_proj[1], d.rowscale1, N_tok, sv.x1, C,
                                 d.drop_p > 0.f ? d.drop_seed : nullptr, s));
     } else {
@@ -219,8 +235,7 @@ int block_fwd(const MdvitBlockDesc& d, const float* x, float* y, Arena& SV, Aren
         g.A = sv.att; g.B = d.proj_w; g.C = sv.x2; g.M = M; g.N = C; g.K = C; g.lda = C; g.ldb = C; g.ldc = C; g.bias = d.proj_b;
         g.e_drop_p = d.drop_p; g.e_key0 = d.key_proj[0]; g.e_key1 = d.key_proj[1]; g.e_rowscale = d.rowscale1; g.e_rows_per_scale = N_tok;
         g.residual = sv.x1; g.ldr = C; g.drop_seed = d.drop_p > 0.f ? d.drop_seed : nullptr;
-        const int rc = gemm_fwd(A, g, s, &d, d.proj_p);
-        if (rc != MDVIT_OK) return rc;
+        BLK_TRY(gemm_fwd(A, d, g, d.proj_p, s));
     }
     // cur2 = LN2(x2);  y = x2 + droppath(drop(fc2(drop(gelu(fc1(cur2))))))                           (mpvit.py:71-78, mdvit.py:356-360)
     const uint32_t* seed = d.drop_p > 0.f ? d.drop_seed : nullptr;
@@ -252,44 +267,55 @@ int block_fwd(const MdvitBlockDesc& d, const float* x, float* y, Arena& SV, Aren
         g.e_drop_p = d.drop_p; g.e_key0 = d.key_fc1[0]; g.e_key1 = d.key_fc1[1]; g.drop_seed = seed;
         if (mode == MLP_RECOMP) { g.C = sv.h; g.C2 = nullptr; }            // gelu(u) only: the backward recomputes u
         else { g.C = sv.u; g.C2 = sv.h; }
-        g.trans_a = 0; g.trans_b = 1; g.allow_split = 0;
-        if (ph_takes(d, d.fc1_p, M, Hd, C, 0)) { const int rc = gemm_planes_nt(A, g, d.fc1_p, s); if (rc != MDVIT_OK) return rc; }
-        else BLK_RUN(mdvit_gemm_f32(&g, s));
+        BLK_TRY(gemm_fwd(A, d, g, d.fc1_p, s, 0));
         gemm_init(g, d);
         g.A = sv.h; g.B = d.fc2_w; g.C = y; g.M = M; g.N = C; g.K = Hd; g.lda = Hd; g.ldb = Hd; g.ldc = C; g.bias = d.fc2_b;
         g.e_drop_p = d.drop_p; g.e_key0 = d.key_fc2[0]; g.e_key1 = d.key_fc2[1]; g.e_rowscale = d.rowscale2; g.e_rows_per_scale = N_tok;
         g.residual = sv.x2; g.ldr = C; g.drop_seed = seed;
-        g.trans_a = 0; g.trans_b = 1; g.allow_split = 0;
-        if (ph_takes(d, d.fc2_p, M, C, Hd, 1)) { const int rc = gemm_planes_nt(A, g, d.fc2_p, s); if (rc != MDVIT_OK) return rc; }
-        else BLK_RUN(mdvit_gemm_f32(&g, s));
+        BLK_TRY(gemm_fwd(A, d, g, d.fc2_p, s, 0));
     }
     return MDVIT_OK;
 }
 
+struct Late { const float* part; int batches, nblk, n0; float* out0; int n1; float* out1; };          // a second-stage reduction put off to the side stream
+
 // A: temporaries only the main stream touches (the caller may free them when the call returns: stream-ordered reuse); S: everything a
-// side-stream kernel reads or writes (must stay alive until the side stream has finished)
-int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBlockStreams& st, const float* x, const float* dy, float* dx, Arena& SV, Arena& A, Arena& S) {
+// side-stream kernel reads or writes (must stay alive until the side stream has finished).  Planning: st, x, dy and dx are NULL
+int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBlockStreams* st, bool have_side, const float* x, const float* dy, float* dx, Arena& SV, Arena& A,
+              Arena& S) {
     const int B = d.B, H = d.H, W = d.W, C = d.C, Hd = d.hidden;
     const long T = (long)B * H * W;
     const int M = (int)T, N_tok = H * W;
     const int mode = mlp_mode(d);
     const bool dgrad_only = G.dgrad_only != 0, want_w = !dgrad_only;
     const int acc = G.accumulate;
-    hipStream_t s = (hipStream_t)st.main, side = s;
+    hipStream_t s = st ? (hipStream_t)st->main : nullptr, side = s;
     Saved sv;
     layout_saved(d, SV, sv);
     if (sdpa_kind(d)) sv.x1 = const_cast<float*>(x);
     const uint32_t* seed = d.drop_p > 0.f ? d.drop_seed : nullptr;
-    const bool fast_ln = C == 64 || C == 128 || C == 320 || C == 512;
-
-    const bool have_side = st.side != nullptr && st.side != st.main;
+    const bool fast_ln = mdvit_fast_ln(C);
     // Second stages of the parameter-gradient reductions (LayerNorm dgamma / dbeta, the fc2 bias column sums): ~20 us each of latency-bound work on four
     // workgroups.  When the gradients ACCUMULATE into buckets nobody reads them before the side stream is joined, so those passes run there (their
     // partial rows live in the side arena) instead of sitting on the data-gradient chain of the main stream.
     const bool defer = want_w && acc != 0 && G.ln_accumulate != 0 && have_side && fast_ln;
-    struct Late { const float* part; int batches, nblk, n0; float* out0; int n1; float* out1; };
     Late late[4];
     int n_late = 0;
+    // One LayerNorm backward of the block (upstream gradient g + g2, `add` joins dx).  dgamma / dbeta go to the gradient outputs, to scratch where nobody wants them (the
+    // generic-C kernel always reduces) or -- deferred -- stay as partial rows in the side arena
+    auto ln_bwd = [&](const float* g, const float* g2, const float* xin, const float* gamma, const float* mean, const float* rstd, const float* add, float* dxo,
+                      float* dg_out, float* db_out, const MdvitLnMask* mask) -> int {
+        const bool lnw = want_w || !fast_ln;
+        const size_t pb = lnw ? mdvit_partials_ws_bytes(2 * C) : 0;
+        void* pw = lnw ? A.take_bytes(pb) : nullptr;
+        float* dg = want_w ? dg_out : (lnw ? A.take((long)d.ln_groups * C) : nullptr);
+        float* db = want_w ? db_out : (lnw ? A.take((long)d.ln_groups * C) : nullptr);
+        if (defer) pw = S.take_bytes(pb);
+        int nb = 0;
+        BLK_RUN(mdvit_ln_bwd(g, g2, xin, gamma, mean, rstd, add, dxo, dg, db, pw, pb, M, C, d.ln_groups, mask, defer ? &nb : nullptr, s));
+        if (defer) late[n_late++] = Late{(const float*)pw, d.ln_groups, nb, C, dg, C, db};
+        return MDVIT_OK;
+    };
     if (want_w && acc == 0) {       // bias gradients ride on column sums that ACCUMULATE: clear the fresh buffers first
         const MdvitZeroItem z[4] = {{G.qkv_b, sizeof(float) * 3 * C}, {G.proj_b, sizeof(float) * C}, {mode == MLP_RC ? nullptr : G.fc1_b, sizeof(float) * Hd},
                                     {mode == MLP_RC ? nullptr : G.fc2_b, sizeof(float) * C}};
@@ -300,7 +326,7 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
     const bool masked = d.drop_p > 0.f || d.rowscale2 != nullptr;
     // The fused kernels of the C = 64 / 128 blocks take dy itself and mask it where they load its rows (the *_masked entries of mlp_rc.hip, mdvit_mlp_mask_config): no
     // mask pass in front of them.  gm2 then exists only where a weight-gradient GEMM reads it (C = 128, full sweep: the data-gradient kernel writes it as gm_out).
-    const bool rc16_path = mode != MLP_RC && mlp_rc16(d) && d.fc2t_p && d.fc1t_p;
+    const bool rc16_path = rc16_bwd(d);
     const int fold_case = !want_w ? MDVIT_MASK_FOLD_AUX : (mode == MLP_RC ? MDVIT_MASK_FOLD_FULL64 : MDVIT_MASK_FOLD_FULL128);
     const bool fold = masked && (mode == MLP_RC || rc16_path) && (g_rc_mask_fold & fold_case) != 0;
     const float m_p = fold ? d.drop_p : 0.f;                                 // the mask descriptor of the *_masked entries: empty without the fold
@@ -344,7 +370,7 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
         if (want_w) {
             const size_t wb = mdvit_mlp_rc_wgrad_ws_bytes(M, C, Hd);
             void* ww = S.take_bytes(wb);
-            if (!A.dry) { const int rc = fork_side(d, st, side); if (rc != MDVIT_OK) return rc; }
+            BLK_RUN(fork_side(*st, side));
             BLK_RUN(mdvit_mlp_rc_wgrad_masked(gm2, sv.cur2, d.fc1_p, d.fc1_b, d.fc2t_p, G.fc1_w, G.fc1_b, G.fc2_w, ww, wb, M, C, Hd, d.drop_p, d.key_fc1[0], d.key_fc1[1],
                                               seed, m_p, d.key_fc2[0], d.key_fc2[1], seed, m_rs, N_tok, acc, side));
         }
@@ -352,10 +378,9 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
     } else {
         if (masked && !fold) BLK_RUN(mdvit_colsum_f32(dy, C, nullptr, gm2, nullptr, 0, M, C, d.drop_p, d.key_fc2[0], d.key_fc2[1], d.rowscale2, N_tok, 0, seed, s));
         MdvitGemmDesc g;
-        int rc = MDVIT_OK;
         const bool hb = hbf16(d);
-        if (hb && !(d.fc2t_p && d.fc1t_p)) return mdvit_set_error(MDVIT_E_SHAPE, "block_bwd: store_bf16 needs the transposed fc weight planes (the 16-token MLP backward)");
-        if (mlp_rc16(d) && d.fc2t_p && d.fc1t_p) {
+        if (hb && !rc16_path) return mdvit_set_error(MDVIT_E_SHAPE, "block_bwd: store_bf16 needs the transposed fc weight planes (the 16-token MLP backward)");
+        if (rc16_path) {
             // u recomputed, du = (gm W2) * gelu'(u) * mask and dcur2 = du W1 in one kernel; du reaches HBM only for the weight gradients
             du = want_w ? S.take(hb ? (T * Hd + 1) / 2 : T * Hd) : nullptr;
             const float* g_in = fold ? dy : gm2;          // fold, full sweep: the kernel writes gm2 (gm_out) for the fc2 weight-gradient GEMM below
@@ -371,18 +396,15 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
             if (mode == MLP_RECOMP) { g.rc_a = sv.cur2; g.rc_lda = C; g.rc_b = d.fc1_w; g.rc_ldb = C; g.rc_bias = d.fc1_b; g.rc_k = C; }
             else { g.gelu_u = sv.u; g.ldu = Hd; }
             g.allow_split = 0;
-            rc = gemm_dgrad(A, d, g, gm2, d.fc2_w, d.fc2_wt, du, M, Hd, C, s, d.fc2t_p);  // du = (gm W2) * gelu'(u) * mask
-            if (rc != MDVIT_OK) return rc;
+            BLK_TRY(gemm_dgrad(A, d, g, gm2, d.fc2_w, d.fc2_wt, du, M, Hd, C, s, d.fc2t_p));  // du = (gm W2) * gelu'(u) * mask
             gemm_init(g, d);
             g.allow_split = 1;
-            rc = gemm_dgrad(A, d, g, du, d.fc1_w, d.fc1_wt, dcur2, M, C, Hd, s, d.fc1t_p);     // dx = du W1
-            if (rc != MDVIT_OK) return rc;
+            BLK_TRY(gemm_dgrad(A, d, g, du, d.fc1_w, d.fc1_wt, dcur2, M, C, Hd, s, d.fc1t_p));     // dx = du W1
         }
         if (want_w) {
-            if (!A.dry) { rc = fork_side(d, st, side); if (rc != MDVIT_OK) return rc; }
-            rc = gemm_wgrad(S, d, gm2, sv.h, G.fc2_w, G.fc2_b, M, C, Hd, acc, side, 0, hb);
-            if (rc == MDVIT_OK) rc = gemm_wgrad(S, d, du, sv.cur2, G.fc1_w, G.fc1_b, M, Hd, C, acc, side, hb, 0);
-            if (rc != MDVIT_OK) return rc;
+            BLK_RUN(fork_side(*st, side));
+            BLK_TRY(gemm_wgrad(S, d, gm2, sv.h, G.fc2_w, G.fc2_b, M, C, Hd, acc, side, 0, hb));
+            BLK_TRY(gemm_wgrad(S, d, du, sv.cur2, G.fc1_w, G.fc1_b, M, Hd, C, acc, side, hb, 0));
         }
     }
     // ---- LN2 (+ the residual branch's gradient, which is dy itself) ---------------------------------------------------------------
@@ -390,44 +412,21 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
     const bool masked1 = d.drop_p > 0.f || d.rowscale1 != nullptr;
     float* dx2 = masked1 ? A.take(T * C) : S.take(T * C);      // (unmasked: it IS the proj weight gradient's operand)
     float* gm1 = masked1 ? S.take(T * C) : dx2;
-    {
-        const bool lnw = want_w || !fast_ln;
-        const size_t pb = lnw ? mdvit_partials_ws_bytes(2 * C) : 0;
-        void* pw = lnw ? A.take_bytes(pb) : nullptr;
-        float* dg = want_w ? G.n2_g : (lnw ? A.take((long)d.ln_groups * C) : nullptr);
-        float* db = want_w ? G.n2_b : (lnw ? A.take((long)d.ln_groups * C) : nullptr);
-        if (!A.dry) mdvit_layernorm_bwd_next_dy2(dcur2_b);
-        if (defer) {
-            void* pws = S.take_bytes(pb);
-            int nb = 0;
-            BLK_RUN(mdvit_layernorm_bwd_parts(dcur2, sv.x2, d.n2_g, sv.mean2, sv.rstd2, dy, dx2, masked1 ? gm1 : nullptr, pws, pb, M, C, d.ln_groups, d.drop_p, d.key_proj[0],
-                                              d.key_proj[1], d.rowscale1, N_tok, seed, s, &nb));
-            late[n_late++] = Late{(const float*)pws, d.ln_groups, nb, C, dg, C, db};
-        } else if (masked1 && fast_ln) {
-            BLK_RUN(mdvit_layernorm_bwd_masked(dcur2, sv.x2, d.n2_g, sv.mean2, sv.rstd2, dy, dx2, gm1, dg, db, pw, pb, M, C, d.ln_groups, d.drop_p, d.key_proj[0],
-                                               d.key_proj[1], d.rowscale1, N_tok, seed, s));
-        } else {
-            BLK_RUN(mdvit_layernorm_bwd(dcur2, sv.x2, d.n2_g, sv.mean2, sv.rstd2, dy, dx2, dg, db, pw, pb, M, C, d.ln_groups, s));
-            if (masked1) BLK_RUN(mdvit_colsum_f32(dx2, C, nullptr, gm1, nullptr, 0, M, C, d.drop_p, d.key_proj[0], d.key_proj[1], d.rowscale1, N_tok, 0, seed, s));
-        }
-    }
+    const bool mask_in_ln = masked1 && fast_ln;          // (defer implies fast_ln)
+    const MdvitLnMask mk1{gm1, d.drop_p, d.key_proj[0], d.key_proj[1], d.rowscale1, N_tok, seed};
+    BLK_TRY(ln_bwd(dcur2, dcur2_b, sv.x2, d.n2_g, sv.mean2, sv.rstd2, dy, dx2, G.n2_g, G.n2_b, mask_in_ln ? &mk1 : nullptr));
+    if (masked1 && !mask_in_ln) BLK_RUN(mdvit_colsum_f32(dx2, C, nullptr, gm1, nullptr, 0, M, C, d.drop_p, d.key_proj[0], d.key_proj[1], d.rowscale1, N_tok, 0, seed, s));
     // ---- proj Linear: data gradient, weight gradient (side) ---------------------------------------------------------------------------
     float* datt = tmp;
     {
         MdvitGemmDesc g;
         gemm_init(g, d);
         g.allow_split = 1;
-        int rc = MDVIT_OK;
-        if (d.precision == 1 && (C == 64 || C == 128) && d.projt_p && M >= 1024) {
-            BLK_RUN(mdvit_linear_rc(gm1, C, d.projt_p, (long)C * C, nullptr, datt, C, M, C, C, 0.f, 0, 0, nullptr, 1, nullptr, 0, nullptr, s));
-        } else {
-            rc = gemm_dgrad(A, d, g, gm1, d.proj_w, d.proj_wt, datt, M, C, C, s, d.projt_p);
-            if (rc != MDVIT_OK) return rc;
-        }
+        if (lin_rc(d, d.projt_p)) BLK_RUN(mdvit_linear_rc(gm1, C, d.projt_p, (long)C * C, nullptr, datt, C, M, C, C, 0.f, 0, 0, nullptr, 1, nullptr, 0, nullptr, s));
+        else BLK_TRY(gemm_dgrad(A, d, g, gm1, d.proj_w, d.proj_wt, datt, M, C, C, s, d.projt_p));
         if (want_w) {
-            if (!A.dry) { rc = fork_side(d, st, side); if (rc != MDVIT_OK) return rc; }
-            rc = gemm_wgrad(S, d, gm1, sv.att, G.proj_w, G.proj_b, M, C, C, acc, side);
-            if (rc != MDVIT_OK) return rc;
+            BLK_RUN(fork_side(*st, side));
+            BLK_TRY(gemm_wgrad(S, d, gm1, sv.att, G.proj_w, G.proj_b, M, C, C, acc, side));
         }
     }
     // ---- attention core + adapter ---------------------------------------------------------------------------------------------------
@@ -463,7 +462,7 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
                                     inl ? G.b3 : nullptr, inl ? G.w5 : nullptr, inl ? G.b5 : nullptr, inl ? G.w7 : nullptr, inl ? G.b7 : nullptr, faws, fab, B, H, W, C,
                                     d.heads, d.s3, d.s5, d.s7, s));
         if (deferred) {
-            if (!A.dry) { const int rc = fork_side(d, st, side); if (rc != MDVIT_OK) return rc; }
+            BLK_RUN(fork_side(*st, side));
             BLK_RUN(mdvit_factoratt_wgrad(sv.qkv, faws, fab, G.w3, G.b3, G.w5, G.b5, G.w7, G.b7, B, H, W, C, d.heads, d.s3, d.s5, d.s7, 1, side));
         }
         if (inl && acc) return mdvit_set_error(MDVIT_E_SHAPE, "block_bwd: accumulating window-weight gradients need the side stream");
@@ -481,38 +480,23 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
         MdvitGemmDesc g;
         gemm_init(g, d);
         g.allow_split = 1;
-        int rc = gemm_dgrad(A, d, g, dqkv, d.qkv_w, d.qkv_wt, dcur1, M, C, 3 * C, s, d.qkvt_p);
-        if (rc != MDVIT_OK) return rc;
+        BLK_TRY(gemm_dgrad(A, d, g, dqkv, d.qkv_w, d.qkv_wt, dcur1, M, C, 3 * C, s, d.qkvt_p));
         if (want_w) {
-            if (!A.dry) { rc = fork_side(d, st, side); if (rc != MDVIT_OK) return rc; }
-            rc = gemm_wgrad(S, d, dqkv, sv.cur1, G.qkv_w, G.qkv_b, M, 3 * C, C, acc, side);
-            if (rc != MDVIT_OK) return rc;
+            BLK_RUN(fork_side(*st, side));
+            BLK_TRY(gemm_wgrad(S, d, dqkv, sv.cur1, G.qkv_w, G.qkv_b, M, 3 * C, C, acc, side));
         }
     }
     // ---- LN1 (+ dx2 along the residual branch) ------------------------------------------------------------------------------------
-    float* dx1 = (sdpa_kind(d) && dx) ? dx : S.take(T * C);          // (Block_adapt: no ConvPosEnc below -- this IS the block's input gradient)
-    {
-        const bool lnw = want_w || !fast_ln;
-        const size_t pb = lnw ? mdvit_partials_ws_bytes(2 * C) : 0;
-        void* pw = lnw ? A.take_bytes(pb) : nullptr;
-        float* dg = want_w ? G.n1_g : (lnw ? A.take((long)d.ln_groups * C) : nullptr);
-        float* db = want_w ? G.n1_b : (lnw ? A.take((long)d.ln_groups * C) : nullptr);
-        if (defer) {
-            void* pws = S.take_bytes(pb);
-            int nb = 0;
-            BLK_RUN(mdvit_layernorm_bwd_parts(dcur1, sv.x1, d.n1_g, sv.mean1, sv.rstd1, dx2, dx1, nullptr, pws, pb, M, C, d.ln_groups, 0.f, 0, 0, nullptr, 1, nullptr, s, &nb));
-            late[n_late++] = Late{(const float*)pws, d.ln_groups, nb, C, dg, C, db};
-        } else {
-            BLK_RUN(mdvit_layernorm_bwd(dcur1, sv.x1, d.n1_g, sv.mean1, sv.rstd1, dx2, dx1, dg, db, pw, pb, M, C, d.ln_groups, s));
-        }
-    }
-    if (n_late > 0 && !A.dry) {          // one fork for the block's deferred second stages: they ACCUMULATE into the LayerNorm / bias buckets
-        const int rcf = fork_side(d, st, side);
-        if (rcf != MDVIT_OK) return rcf;
+    // Block_adapt has no ConvPosEnc below: dx1 IS the block's input gradient and goes straight to dx where the caller wants one.  The slot is taken either way -- what the
+    // pass takes must not hang on dx, which the planning pass does not see (a block input that needs no gradient once wrote this tensor past the side arena)
+    float* dx1 = S.take(T * C);
+    if (sdpa_kind(d) && dx) dx1 = dx;
+    BLK_TRY(ln_bwd(dcur1, nullptr, sv.x1, d.n1_g, sv.mean1, sv.rstd1, dx2, dx1, G.n1_g, G.n1_b, nullptr));
+    if (n_late > 0) {          // one fork for the block's deferred second stages: they ACCUMULATE into the LayerNorm / bias buckets
+        BLK_RUN(fork_side(*st, side));
         for (int i = 0; i < n_late; ++i) {
             const Late& L = late[i];
-            const int rc = mdvit_reduce_partials_batched2_acc(L.part, L.batches, L.nblk, L.n0, L.out0, L.n1, L.out1, 1, side);
-            if (rc != MDVIT_OK) return rc;
+            BLK_RUN(mdvit_reduce_partials_batched2_acc(L.part, L.batches, L.nblk, L.n0, L.out0, L.n1, L.out1, 1, side));
         }
     }
     // ---- ConvPosEnc -----------------------------------------------------------------------------------------------------------------
@@ -521,7 +505,7 @@ int block_bwd(const MdvitBlockDesc& d, const MdvitBlockGrads& G, const MdvitBloc
     if (want_w) {
         const size_t pb = mdvit_partials_ws_bytes(10 * C);
         void* pw = S.take_bytes(pb);
-        if (acc && !A.dry) { const int rc = fork_side(d, st, side); if (rc != MDVIT_OK) return rc; }
+        if (acc) BLK_RUN(fork_side(*st, side));
         BLK_RUN(mdvit_dwconv3x3_bwd(dx1, x, d.cpe_w, nullptr, G.cpe_w, G.cpe_b, pw, pb, B, H, W, C, 1, 1, acc, acc ? side : s));
     }
     return MDVIT_OK;
@@ -546,7 +530,7 @@ int check_desc(const MdvitBlockDesc& d, const char* what) {
 
 extern "C" size_t mdvit_block_save_bytes(const MdvitBlockDesc* d) {
     if (!d || check_desc(*d, "block_save_bytes") != MDVIT_OK) return 0;
-    Arena SV{nullptr, 0, 0, true};
+    Arena SV = Arena::plan();
     Saved sv;
     layout_saved(*d, SV, sv);
     return SV.off;
@@ -554,7 +538,7 @@ extern "C" size_t mdvit_block_save_bytes(const MdvitBlockDesc* d) {
 
 extern "C" size_t mdvit_block_fwd_ws_bytes(const MdvitBlockDesc* d) {
     if (!d || check_desc(*d, "block_fwd_ws_bytes") != MDVIT_OK) return 0;
-    Arena SV{nullptr, 0, 0, true}, A{nullptr, 0, 0, true};
+    Arena SV = Arena::plan(), A = Arena::plan();
     if (block_fwd(*d, nullptr, nullptr, SV, A, nullptr) != MDVIT_OK) return 0;
     return A.off + 256;
 }
@@ -569,19 +553,16 @@ extern "C" int mdvit_block_fwd(const MdvitBlockDesc* d, const float* x, float* y
                     mdvit_block_save_bytes(d), save_bytes);
     const size_t need = mdvit_block_fwd_ws_bytes(d);
     MDVIT_CHECK_ARG(ws_bytes >= need && ws, MDVIT_E_WORKSPACE, "block_fwd: workspace too small: need %zu bytes (mdvit_block_fwd_ws_bytes), got %zu", need, ws_bytes);
-    Arena SV{(char*)save, 0, save_bytes, false}, A{(char*)ws, 0, ws_bytes, false};
-    return block_fwd(*d, x, y, SV, A, (hipStream_t)stream);
+    Arena SV = Arena::over("save", save, save_bytes), A = Arena::over("workspace", ws, ws_bytes);
+    try { return block_fwd(*d, x, y, SV, A, (hipStream_t)stream); }
+    catch (const ArenaOverflow&) { return MDVIT_E_WORKSPACE; }
 }
 
 extern "C" size_t mdvit_block_bwd_ws_bytes(const MdvitBlockDesc* d, const MdvitBlockGrads* g, int32_t with_side_stream, size_t* side_bytes) {
     if (side_bytes) *side_bytes = 0;
     if (!d || !g || check_desc(*d, "block_bwd_ws_bytes") != MDVIT_OK) return 0;
-    Arena SV{nullptr, 0, 0, true}, A{nullptr, 0, 0, true}, S{nullptr, 0, 0, true};
-    MdvitBlockStreams st;
-    memset(&st, 0, sizeof(st));
-    st.main = (void*)1; st.side = with_side_stream ? (void*)2 : (void*)1;          // only compared, never used: the run is dry
-    float dummy = 0.f;
-    if (block_bwd(*d, *g, st, nullptr, &dummy, &dummy, SV, A, S) != MDVIT_OK) return 0;
+    Arena SV = Arena::plan(), A = Arena::plan(), S = Arena::plan();
+    if (block_bwd(*d, *g, nullptr, with_side_stream != 0, nullptr, nullptr, nullptr, SV, A, S) != MDVIT_OK) return 0;
     if (side_bytes) *side_bytes = S.off + 256;
     return A.off + 256;
 }
@@ -589,14 +570,14 @@ extern "C" size_t mdvit_block_bwd_ws_bytes(const MdvitBlockDesc* d, const MdvitB
 extern "C" int mdvit_block_bwd(const MdvitBlockDesc* d, const MdvitBlockGrads* g, const MdvitBlockStreams* st, const float* x, const void* save, size_t save_bytes,
                                const float* dy, float* dx, void* ws, size_t ws_bytes, void* ws_side, size_t ws_side_bytes) {
     MDVIT_CHECK_ARG(d && g && st && x && save && dy && ws && ws_side, MDVIT_E_SHAPE, "block_bwd: null argument");
-    mdvit_layernorm_bwd_next_dy2(nullptr);       // (a call that failed between announcing a second dy partial and the LayerNorm backward must not leave it behind)
     const int rc = check_desc(*d, "block_bwd");
     if (rc != MDVIT_OK) return rc;
     MDVIT_CHECK_ARG(aligned16(x) && aligned16(dy) && (!dx || aligned16(dx)) && (reinterpret_cast<uintptr_t>(save) & 255) == 0 && (reinterpret_cast<uintptr_t>(ws) & 255) == 0 &&
                         (reinterpret_cast<uintptr_t>(ws_side) & 255) == 0, MDVIT_E_ALIGN, "block_bwd: x / dy / dx must be 16-byte, save / ws 256-byte aligned");
     MDVIT_CHECK_ARG(save_bytes >= mdvit_block_save_bytes(d), MDVIT_E_WORKSPACE, "block_bwd: save buffer too small");
+    const bool have_side = st->side != nullptr && st->side != st->main;
     size_t need_side = 0;
-    const size_t need = mdvit_block_bwd_ws_bytes(d, g, st->side != nullptr && st->side != st->main, &need_side);
+    const size_t need = mdvit_block_bwd_ws_bytes(d, g, have_side, &need_side);
     MDVIT_CHECK_ARG(ws_bytes >= need && ws_side_bytes >= need_side, MDVIT_E_WORKSPACE,
                     "block_bwd: workspace too small: need %zu + %zu bytes (mdvit_block_bwd_ws_bytes), got %zu + %zu", need, need_side, ws_bytes, ws_side_bytes);
     if (!g->dgrad_only) {
@@ -605,8 +586,9 @@ extern "C" int mdvit_block_bwd(const MdvitBlockDesc* d, const MdvitBlockGrads* g
                         "block_bwd: null gradient output");
     }
     MDVIT_CHECK_ARG(!d->label || g->e_out || (g->da_w1 && g->da_b1 && g->da_w2 && g->da_b2), MDVIT_E_SHAPE, "block_bwd: the adapter's gradient outputs are missing");
-    MDVIT_CHECK_ARG(d->precision == 0 || (d->qkv_wt && d->proj_wt && (mlp_mode(*d) == MLP_RC || (mlp_rc16(*d) && d->fc2t_p && d->fc1t_p) || (d->fc1_wt && d->fc2_wt))), MDVIT_E_SHAPE,
+    MDVIT_CHECK_ARG(d->precision == 0 || (d->qkv_wt && d->proj_wt && (mlp_mode(*d) == MLP_RC || rc16_bwd(*d) || (d->fc1_wt && d->fc2_wt))), MDVIT_E_SHAPE,
                     "block_bwd: the bf16x3 data-gradient GEMMs need the transposed weights");
-    Arena SV{(char*)const_cast<void*>(save), 0, save_bytes, false}, A{(char*)ws, 0, ws_bytes, false}, S{(char*)ws_side, 0, ws_side_bytes, false};
-    return block_bwd(*d, *g, *st, x, dy, dx, SV, A, S);
+    Arena SV = Arena::over("save", save, save_bytes), A = Arena::over("workspace", ws, ws_bytes), S = Arena::over("side workspace", ws_side, ws_side_bytes);
+    try { return block_bwd(*d, *g, st, have_side, x, dy, dx, SV, A, S); }
+    catch (const ArenaOverflow&) { return MDVIT_E_WORKSPACE; }
 }

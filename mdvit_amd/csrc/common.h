@@ -63,18 +63,21 @@ int mdvit_reduce_partials_batched(const float* part, int batches, int nblk, int 
 // batched with two outputs per batch: out0 [batch][n0], out1 [batch][n1]; partial rows are [n0 | n1] wide
 int mdvit_reduce_partials_batched2(const float* part, int batches, int nblk, int n0, float* out0, int n1, float* out1, hipStream_t stream);
 int mdvit_reduce_partials_batched2_acc(const float* part, int batches, int nblk, int n0, float* out0, int n1, float* out1, int accumulate, hipStream_t stream);
-// first stages alone (norm.hip): the partial rows stay in `ws`, *nblk of them per batch; the caller runs the second stage on a stream of its choice
-int mdvit_layernorm_bwd_parts(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* add, float* dx,
-                              float* dx_masked, void* ws, size_t ws_bytes, int M, int C, int groups, float drop_p, uint32_t key0, uint32_t key1,
-                              const float* rowscale, int rows_per_scale, const uint32_t* seed, hipStream_t stream, int* nblk);
+// the channel counts of the 16-row LayerNorm kernels (norm.hip: the encoder stages' widths); block.hip plans its LayerNorm backward calls by the same rule
+static inline bool mdvit_fast_ln(int C) { return C == 64 || C == 128 || C == 320 || C == 512; }
+// The LayerNorm backward with everything the block entry asks of it (norm.hip; the public entries are this with dy2 = NULL).  All optional, C as mdvit_fast_ln:
+//   dy2: the upstream gradient is dy + dy2;  mask: dx * dropout mask * DropPath row scale as a second output;
+//   defer_nblk: first stage alone -- the partial rows stay in `ws`, *defer_nblk of them per group, and the caller runs the second stage on a stream of its choice
+struct MdvitLnMask { float* out; float drop_p; uint32_t key0, key1; const float* rowscale; int rows_per_scale; const uint32_t* seed; };
+int mdvit_ln_bwd(const float* dy, const float* dy2, const float* x, const float* gamma, const float* mean, const float* rstd, const float* add, float* dx,
+                 float* dgamma, float* dbeta, void* ws, size_t ws_bytes, int M, int C, int groups, const MdvitLnMask* mask, int* defer_nblk, hipStream_t stream);
+// column sums, first stage alone (norm.hip), as defer_nblk above
 int mdvit_colsum_parts(const float* A, long lda, float* masked, void* ws, size_t ws_bytes, int M, int N, float drop_p, uint32_t key0, uint32_t key1,
                        const float* rowscale, int rows_per_scale, const uint32_t* seed, hipStream_t stream, int* nblk);
 // mdvit_mlp_mask_config (mlp_rc.hip): which MLP backward cases of the C = 64 / 128 blocks take the unmasked upstream gradient and mask it on load
 constexpr int MDVIT_MASK_FOLD_AUX = 2, MDVIT_MASK_FOLD_FULL128 = 4, MDVIT_MASK_FOLD_FULL64 = 8;
 constexpr int MDVIT_MASK_FOLD_DEFAULT = MDVIT_MASK_FOLD_AUX | MDVIT_MASK_FOLD_FULL128 | MDVIT_MASK_FOLD_FULL64;
 extern int g_rc_mask_fold;
-// the NEXT LayerNorm backward call of this thread reads its upstream gradient as dy + dy2 (norm.hip; consumed by that call)
-void mdvit_layernorm_bwd_next_dy2(const float* dy2);
 constexpr int MDVIT_MAX_PARTIAL_ROWS = 2048;        // every partial-row reduction launches at most this many workgroups
 #define MDVIT_CHECK_PARTIALS_WS(ws, ws_bytes, nblk, n, what)                                                              \
     MDVIT_CHECK_ARG((ws) != nullptr && (ws_bytes) >= sizeof(float) * (size_t)(nblk) * (size_t)(n), MDVIT_E_WORKSPACE,    \

@@ -882,7 +882,7 @@ __device__ __forceinline__ rc_bf16x8 rc_tr8(const char* plane, int t0, int col0,
 // lane <-> hidden unit, but dx contracts over hidden: every wave writes its du^T [32 hidden][32 tokens] (hi / lo planes) to LDS, and after a barrier wave (cblk, tblk) forms
 // the 16 x 16 block dx^T[16 cblk ..][16 tblk ..] over ALL 256 hidden units of the role on v_mfma_f32_16x16x32_bf16 -- A = W1^T rows (the role's [64][256] slice, resident
 // in LDS), B = du^T read back with ds_read_b64_tr_b16 (k = hidden down the rows) -- so no partial sums cross waves.  Roles (256-wide hidden ranges) write their own
-// dx partial [role][tokens][C]; the consumer adds them (mdvit_layernorm_bwd's dy2, or rc_sum_parts_kernel).
+// dx partial [role][tokens][C]; the consumer adds them (the dy2 argument of mdvit_ln_bwd, or rc_sum_parts_kernel).
 #define RC16_MFMA3_BWDP(P1, acc, ah, al, bh, bl)                                    \
     do {                                                                            \
         if constexpr (!(P1)) {                                                      \
@@ -2125,7 +2125,7 @@ extern "C" int mdvit_mlp_rc_wgrad_masked(const float* g, const float* x, const v
 
 /* The whole backward of the C = 64 MLP in ONE kernel + its partial-sum fold (round 5): mdvit_mlp_rc_dgrad and mdvit_mlp_rc_wgrad recompute u = x W1^T + b1, d = gm W2 and
  * the activation twice; here they are formed once and feed all three products -- dW1 = du^T x, dW2 = gm^T h (as mdvit_mlp_rc_wgrad, bit for bit) and dx = du W1.
- * dx_parts [hidden / 256][M][C]: one partial of dx per 256-wide hidden role (the consumer adds them: mdvit_layernorm_bwd's dy2, mdvit_sum_batch); hidden in {256, 512}. */
+ * dx_parts [hidden / 256][M][C]: one partial of dx per 256-wide hidden role (the consumer adds them: the dy2 argument of mdvit_ln_bwd, mdvit_sum_batch); hidden in {256, 512}. */
 static int rc_bwd_impl(const RcMask* mk, const float* gm, const float* x, const void* W1p, const float* b1, const void* W2tp, const void* W1tp, float* dx_parts,
                        float* dW1, float* db1, float* dW2, void* ws, size_t ws_bytes, int32_t M, int32_t C, int32_t Hd, float drop_p,
                        uint32_t key1_0, uint32_t key1_1, const uint32_t* drop_seed, int32_t accumulate, void* stream) {

@@ -789,7 +789,7 @@ extern "C" int mdvit_layernorm_fwd(const float* x, const float* gamma, const flo
     MDVIT_CHECK_ARG(M > 0 && C > 0 && C <= 1024, MDVIT_E_SHAPE, "layernorm_fwd: need 0 < C <= 1024 (M=%d C=%d)", M, C);
     MDVIT_CHECK_ARG(groups > 0 && M % groups == 0, MDVIT_E_SHAPE, "layernorm_fwd: M=%d is not a multiple of groups=%d", M, groups);
     const int Mg = M / groups;                 // rows per parameter group (kernels take the per-group row count; grid.y = group)
-    if (C == 64 || C == 128 || C == 320 || C == 512) {
+    if (mdvit_fast_ln(C)) {
         dim3 grid16(min(cdiv(Mg, 16), max(1, 4096 / groups)), groups);
         if (C == 64) hipLaunchKernelGGL((ln_fwd16_kernel<1>), grid16, dim3(256), 0, s, x, gamma, beta, y, mean, rstd, Mg, eps);
         else if (C == 128) hipLaunchKernelGGL((ln_fwd16_kernel<2>), grid16, dim3(256), 0, s, x, gamma, beta, y, mean, rstd, Mg, eps);
@@ -804,74 +804,51 @@ extern "C" int mdvit_layernorm_fwd(const float* x, const float* gamma, const flo
     return MDVIT_OK;
 }
 
-// A second upstream-gradient partial for the NEXT LayerNorm backward call of this thread (block.hip: the C = 64 MLP backward in one kernel leaves dx as one partial
-// per 256-wide hidden role; the LayerNorm in front of the MLP adds them while it reads them -- no separate sum pass).  EVERY public LayerNorm backward entry takes
-// (reads and clears) it as its first statement, before any argument check can return: a call that fails early must not leave the pointer armed for a later,
-// unrelated LayerNorm backward of this thread.
-static thread_local const float* g_ln_dy2 = nullptr;
-void mdvit_layernorm_bwd_next_dy2(const float* dy2) { g_ln_dy2 = dy2; }
-static inline const float* ln_take_dy2() { const float* p = g_ln_dy2; g_ln_dy2 = nullptr; return p; }
-
-static int layernorm_bwd_impl(const float* dy, const float* dy2, const float* x, const float* gamma, const float* mean, const float* rstd,
-                              const float* add, float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
-                              int32_t M, int32_t C, int32_t groups, const LnMasked& mk, void* stream, int* defer_nblk = nullptr);
-
 // dgamma / dbeta: [groups, C] each
 extern "C" int mdvit_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                                    const float* add, float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
                                    int32_t M, int32_t C, int32_t groups, void* stream) {
-    const float* dy2 = ln_take_dy2();
-    LnMasked mk; memset(&mk, 0, sizeof(mk));
-    return layernorm_bwd_impl(dy, dy2, x, gamma, mean, rstd, add, dx, dgamma, dbeta, ws, ws_bytes, M, C, groups, mk, stream);
+    return mdvit_ln_bwd(dy, nullptr, x, gamma, mean, rstd, add, dx, dgamma, dbeta, ws, ws_bytes, M, C, groups, nullptr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int mdvit_layernorm_bwd_masked(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                                           const float* add, float* dx, float* dx_masked, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
                                           int32_t M, int32_t C, int32_t groups, float drop_p, uint32_t key0, uint32_t key1, const float* rowscale,
                                           int32_t rows_per_scale, const uint32_t* seed, void* stream) {
-    const float* dy2 = ln_take_dy2();
-    MDVIT_CHECK_ARG(C == 64 || C == 128 || C == 320 || C == 512, MDVIT_E_SHAPE, "layernorm_bwd_masked: C=%d not built (64/128/320/512)", C);
-    MDVIT_CHECK_ARG(dx_masked != nullptr && drop_p >= 0.f && drop_p < 1.f && (rowscale == nullptr || rows_per_scale > 0), MDVIT_E_SHAPE,
-                    "layernorm_bwd_masked: bad mask arguments");
-    MDVIT_CHECK_ARG((long)M * C < (1L << 32), MDVIT_E_SHAPE, "layernorm_bwd_masked: dropout index space exceeds 2^32");
-    LnMasked mk; memset(&mk, 0, sizeof(mk));
-    mk.out = dx_masked; mk.drop_p = drop_p; mk.k0 = key0; mk.k1 = key1; mk.thresh = mdvit_drop_thresh(drop_p);
-    mk.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; mk.rowscale = rowscale; mk.rows_per_scale = rows_per_scale > 0 ? rows_per_scale : 1; mk.seed = seed;
-    return layernorm_bwd_impl(dy, dy2, x, gamma, mean, rstd, add, dx, dgamma, dbeta, ws, ws_bytes, M, C, groups, mk, stream);
+    const MdvitLnMask mask{dx_masked, drop_p, key0, key1, rowscale, rows_per_scale, seed};
+    return mdvit_ln_bwd(dy, nullptr, x, gamma, mean, rstd, add, dx, dgamma, dbeta, ws, ws_bytes, M, C, groups, &mask, nullptr, (hipStream_t)stream);
 }
 
-// The LayerNorm backward WITHOUT its second stage: the partial rows [groups][*nblk][dgamma | dbeta] stay in `ws`; the caller adds them up
-// (mdvit_reduce_partials_batched2_acc), on any stream ordered after this one -- block.hip does it on the weight-gradient stream.
-int mdvit_layernorm_bwd_parts(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* add, float* dx,
-                              float* dx_masked, void* ws, size_t ws_bytes, int M, int C, int groups, float drop_p, uint32_t key0, uint32_t key1,
-                              const float* rowscale, int rows_per_scale, const uint32_t* seed, hipStream_t stream, int* nblk) {
-    const float* dy2 = ln_take_dy2();
-    MDVIT_CHECK_ARG(C == 64 || C == 128 || C == 320 || C == 512, MDVIT_E_SHAPE, "layernorm_bwd_parts: C=%d not built (64/128/320/512)", C);
-    MDVIT_CHECK_ARG(nblk != nullptr && ws != nullptr, MDVIT_E_SHAPE, "layernorm_bwd_parts: null argument");
+// The LayerNorm backward behind both entries above and behind block.hip (declared in common.h).
+//   dy2: a second partial of the upstream gradient, added to dy while it is read (the C = 64 MLP backward in one kernel leaves dx as one partial per 256-wide hidden
+//        role: no separate sum pass);
+//   mask: the second output dx * dropout mask * DropPath row scale (LnMasked);
+//   defer_nblk: the first stage alone -- the partial rows [groups][*defer_nblk][dgamma | dbeta] stay in `ws` and the caller adds them up
+//        (mdvit_reduce_partials_batched2_acc) on any stream ordered after this one; dgamma / dbeta are not written.
+// All three are built into the 16-row kernels of the encoder widths only (mdvit_fast_ln).
+int mdvit_ln_bwd(const float* dy, const float* dy2, const float* x, const float* gamma, const float* mean, const float* rstd, const float* add, float* dx,
+                 float* dgamma, float* dbeta, void* ws, size_t ws_bytes, int M, int C, int groups, const MdvitLnMask* mask, int* defer_nblk, hipStream_t s) {
+    MDVIT_CHECK_ARG(mdvit_fast_ln(C) || (!dy2 && !mask && !defer_nblk), MDVIT_E_SHAPE,
+                    "layernorm_bwd: C=%d not built (64/128/320/512) for a second dy partial, a masked output or a deferred second stage", C);
+    MDVIT_CHECK_ARG(aligned16(dy2), MDVIT_E_ALIGN, "layernorm_bwd: the second dy partial must be 16-byte aligned");
+    MDVIT_CHECK_ARG(!defer_nblk || ws != nullptr, MDVIT_E_SHAPE, "layernorm_bwd: the deferred second stage needs a workspace");
     LnMasked mk; memset(&mk, 0, sizeof(mk));
-    if (dx_masked) {
-        MDVIT_CHECK_ARG((long)M * C < (1L << 32), MDVIT_E_SHAPE, "layernorm_bwd_parts: dropout index space exceeds 2^32");
-        mk.out = dx_masked; mk.drop_p = drop_p; mk.k0 = key0; mk.k1 = key1; mk.thresh = mdvit_drop_thresh(drop_p);
-        mk.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; mk.rowscale = rowscale; mk.rows_per_scale = rows_per_scale > 0 ? rows_per_scale : 1; mk.seed = seed;
-    }
-    float dummy;
-    return layernorm_bwd_impl(dy, dy2, x, gamma, mean, rstd, add, dx, &dummy, &dummy, ws, ws_bytes, M, C, groups, mk, stream, nblk);
-}
-
-static int layernorm_bwd_impl(const float* dy, const float* dy2, const float* x, const float* gamma, const float* mean, const float* rstd,
-                              const float* add, float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
-                              int32_t M, int32_t C, int32_t groups, const LnMasked& mk_in, void* stream, int* defer_nblk) {
-    hipStream_t s = (hipStream_t)stream;
-    LnMasked mk = mk_in;
     mk.dy2 = dy2;
-    MDVIT_CHECK_ARG(mk.dy2 == nullptr || ((C == 64 || C == 128 || C == 320 || C == 512) && aligned16(mk.dy2)), MDVIT_E_SHAPE, "layernorm_bwd: a second dy partial needs C in 64/128/320/512");
+    if (mask) {
+        MDVIT_CHECK_ARG(mask->out != nullptr && mask->drop_p >= 0.f && mask->drop_p < 1.f && (mask->rowscale == nullptr || mask->rows_per_scale > 0), MDVIT_E_SHAPE,
+                        "layernorm_bwd_masked: bad mask arguments");
+        MDVIT_CHECK_ARG((long)M * C < (1L << 32), MDVIT_E_SHAPE, "layernorm_bwd_masked: dropout index space exceeds 2^32");
+        mk.out = mask->out; mk.drop_p = mask->drop_p; mk.k0 = mask->key0; mk.k1 = mask->key1; mk.thresh = mdvit_drop_thresh(mask->drop_p);
+        mk.inv_keep = mask->drop_p > 0.f ? 1.f / (1.f - mask->drop_p) : 1.f; mk.rowscale = mask->rowscale;
+        mk.rows_per_scale = mask->rows_per_scale > 0 ? mask->rows_per_scale : 1; mk.seed = mask->seed;
+    }
     MDVIT_CHECK_ARG(M > 0 && C > 0 && C <= 1024, MDVIT_E_SHAPE, "layernorm_bwd: need 0 < C <= 1024 (M=%d C=%d)", M, C);
     MDVIT_CHECK_ARG(groups > 0 && groups <= 64 && M % groups == 0, MDVIT_E_SHAPE, "layernorm_bwd: M=%d is not a multiple of groups=%d", M, groups);
     const int Mg = M / groups;
-    const bool want_params = dgamma != nullptr || dbeta != nullptr;        // both NULL: data gradient only (no partial sums, no reduction launch)
+    const bool want_params = defer_nblk != nullptr || dgamma != nullptr || dbeta != nullptr;        // none: data gradient only (no partial sums, no reduction launch)
     float* part = want_params ? (float*)ws : nullptr;                      // [group][workgroup][dgamma | dbeta]
     int nblk;
-    if (C == 64 || C == 128 || C == 320 || C == 512) {
+    if (mdvit_fast_ln(C)) {
         // rows per workgroup: 64 (four passes of 16) where the grid fills the chip anyway; 16 for the short tensors of stages 2 / 3 (C >= 320: 4096-16384 rows at
         // bs=4), which otherwise run as 256 four-wave workgroups with four dependent load rounds each (MDVIT_LN_BWD_ROWS=64: the old grid, A/B)
         static const int rows_env = [] { const char* e = getenv("MDVIT_LN_BWD_ROWS"); return e ? atoi(e) : 0; }();
@@ -1021,7 +998,7 @@ extern "C" int mdvit_bn_rowdot_bwd(const float* g, const float* y, const float* 
 static int colsum_impl(const float* A, int64_t lda, float* out, float* masked, void* ws, size_t ws_bytes, int32_t M, int32_t N, float drop_p,
                        uint32_t key0, uint32_t key1, const float* rowscale, int32_t rows_per_scale, int32_t accumulate, const uint32_t* seed, void* stream, int* defer_nblk);
 
-// column sums WITHOUT the second stage: the partial rows [*nblk][N] stay in `ws` (see mdvit_layernorm_bwd_parts)
+// column sums WITHOUT the second stage: the partial rows [*nblk][N] stay in `ws` (see mdvit_ln_bwd's defer_nblk)
 int mdvit_colsum_parts(const float* A, long lda, float* masked, void* ws, size_t ws_bytes, int M, int N, float drop_p, uint32_t key0, uint32_t key1,
                        const float* rowscale, int rows_per_scale, const uint32_t* seed, hipStream_t stream, int* nblk) {
     float dummy;

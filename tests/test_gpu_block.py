@@ -220,3 +220,94 @@ def test_mixed_mode_stores_the_c128_mlp_hidden_tensors_as_bf16(monkeypatch):
         else:
             assert torch.equal(a, b), f"{n} differs by {rel:.2e}"
     assert len(moved) == 6, moved          # two blocks x (fc1.weight, fc1.bias, fc2.weight)
+
+
+# ---- the DeiT Block_adapt of TransFuse through the same entry (MdvitBlockDesc.attn_kind = 1) --------------------------------------------------------------------
+
+def make_deit_block(dim, heads, seed=0):
+    from mdvit_amd.transfuse import Block_adapt
+    torch.manual_seed(seed)
+    blk = Block_adapt(dim, heads, 4.0)
+    with torch.no_grad():
+        for n, p in blk.named_parameters():                 # (the parameter holders are created uninitialised: the model's own init runs on the whole network)
+            if p.dim() > 1:
+                p.copy_(torch.randn_like(p) * 0.05)
+            else:
+                p.copy_(torch.randn_like(p) * 0.1 + (1.0 if n.startswith("norm") and n.endswith("weight") else 0.0))
+    return blk.to(dev()).train()
+
+
+def run_deit(blk, x, label, g, entry, monkeypatch, requires_grad=True):
+    from mdvit_amd import ops
+    monkeypatch.setattr(ops, "_deit_block_entry", entry)
+    for p in blk.parameters():
+        p.grad = None
+    xin = x.clone().requires_grad_(requires_grad)
+    y = blk(xin, label)
+    assert (type(y.grad_fn).__name__ == "_SerialBlockBackward") == entry          # the path under test is the path that ran
+    y.backward(g)
+    ops.join_side_stream()
+    torch.cuda.synchronize()
+    return y.detach(), xin.grad, {n: (None if p.grad is None else p.grad.clone()) for n, p in blk.named_parameters()}
+
+
+def _deit_inputs(dim):
+    B, N = 2, 256
+    torch.manual_seed(3)
+    x = torch.randn(B, N, dim, device=dev())
+    label = torch.nn.functional.one_hot(torch.tensor([2, 0]), 4).float().to(dev())
+    g = torch.randn(B, N, dim, device=dev())
+    return x, label, g
+
+
+@pytest.mark.parametrize("requires_grad", [True, False])
+@pytest.mark.parametrize("dim,heads", [(64, 1), (128, 2), (384, 6)])
+def test_deit_block_entry_equals_operator_path(dim, heads, requires_grad, gemm_precision, monkeypatch):
+    """Block_adapt (vision_transformer.py:191-211) through the C-level entry against its operator-level path: y and dx bit for bit, parameter gradients by the rules of
+    test_block_entry_equals_operator_path.  requires_grad=False is a block whose input needs no gradient (a frozen patch embedding in front of the first block): the
+    entry gets dx = NULL and the LayerNorm-1 backward writes its data gradient into a slot of the side arena -- one the sizing call used not to count, so the kernel
+    wrote [tokens, C] floats past the buffer.  dx is None then, and every parameter gradient still matches."""
+    x, label, g = _deit_inputs(dim)
+    blk = make_deit_block(dim, heads)
+    ref = run_deit(blk, x, label, g, False, monkeypatch, requires_grad)
+    got = run_deit(blk, x, label, g, True, monkeypatch, requires_grad)
+    assert torch.equal(got[0], ref[0]), f"y differs by {float((got[0] - ref[0]).abs().max()):.3e}"
+    if requires_grad:
+        assert torch.equal(got[1], ref[1]), f"dx differs by {float((got[1] - ref[1]).abs().max()):.3e}"
+    else:
+        assert got[1] is None and ref[1] is None
+    for n in ref[2]:
+        a, b = got[2][n], ref[2][n]
+        assert a is not None and b is not None, n
+        if "domain_layer" in n or (gemm_precision == "fp32" and n.endswith(".bias")):          # float atomics: last-bit differences run to run
+            assert float((a - b).abs().max()) <= 2e-6 * max(float(b.abs().max()), 1e-12), n
+        else:
+            assert torch.equal(a, b), f"{n} differs by {float((a - b).abs().max()):.3e}"
+
+
+def test_deit_block_entry_with_gradient_buckets_and_side_stream(monkeypatch):
+    """the same block with its weight gradients accumulated into persistent buffers on the side stream (the pattern of
+    test_block_entry_with_gradient_buckets_and_side_stream): the forks, the side arena and the deferred second-stage reductions of attn_kind 1"""
+    from mdvit_amd import ops
+    from mdvit_amd._lib import call
+    x, label, g = _deit_inputs(64)
+    blk = make_deit_block(64, 1)
+    monkeypatch.setattr(ops, "_mlp_rc_bwd", "0")           # both paths on the two-kernel form of the C = 64 MLP backward (see the SerialBlock_adapt test above)
+    call("mdvit_block_config", 0)
+    ref = run_deit(blk, x, label, g, False, monkeypatch)
+    sinks = {p: torch.full_like(p, 0.25) for p in blk.parameters()}
+    ops.enable_side_stream(True)
+    ops.set_grad_sinks(sinks)
+    try:
+        for _ in range(3):                             # repeated: a missing cross-stream dependency shows as run-to-run drift
+            for v in sinks.values():
+                v.fill_(0.25)
+            got = run_deit(blk, x, label, g, True, monkeypatch)
+            assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
+            for n, p in blk.named_parameters():
+                total = sinks[p] - 0.25 + (p.grad if p.grad is not None else 0)
+                assert float((total - ref[2][n]).abs().max()) <= 1e-6 * max(float(ref[2][n].abs().max()), 1e-12), n
+    finally:
+        ops.set_grad_sinks(None)
+        ops.enable_side_stream(False)
+        call("mdvit_block_config", 1)

@@ -230,6 +230,96 @@ def test_block_entry_routing_predicates_without_gpu():
         ops.set_gemm_precision(prev)
 
 
+_BLK_PTR = 4096          # a 256-aligned stand-in for every pointer: the planning and the argument checks only compare pointers with NULL
+
+
+def _block_entry_desc(B, H, W, Cn, heads, hidden, attn_kind):
+    from mdvit_amd import _lib
+    d = _lib.BlockDesc()
+    d.B, d.H, d.W, d.C, d.heads, d.hidden, d.attn_kind = B, H, W, Cn, heads, hidden, attn_kind
+    d.s3, d.s5, d.s7 = 2, 3, 3
+    d.ln_groups, d.precision, d.eps = 1, 1, 1e-6
+    d.label, d.D, d.da_hidden = _BLK_PTR, 4, 16
+    for n in _lib.BLOCK_PARAMS + ("qkv_wt", "proj_wt", "fc1_wt", "fc2_wt", "fc1_p", "fc2_p", "fc2t_p", "fc1t_p", "qkv_p", "proj_p", "projt_p", "qkvt_p"):
+        setattr(d, n, _BLK_PTR)
+    if attn_kind == 0:                                 # SerialBlock_adapt: dropout and both DropPath row scales; the DeiT Block_adapt has neither
+        d.drop_p, d.drop_seed, d.rowscale1, d.rowscale2 = 0.1, _BLK_PTR, _BLK_PTR, _BLK_PTR
+    return d
+
+
+def _block_entry_grads(accumulate, dgrad_only):
+    from mdvit_amd import _lib
+    G = _lib.BlockGrads()
+    for n in _lib.BLOCK_PARAMS:
+        setattr(G, n, _BLK_PTR)
+    G.accumulate = G.ln_accumulate = accumulate
+    G.dgrad_only = dgrad_only
+    return G
+
+
+_BLK_SETTINGS = ((0, 0, 0), (1, 0, 1), (0, 1, 0))          # (accumulate = ln_accumulate, dgrad_only, with_side_stream)
+# (B, H, W, C, heads, hidden, attn_kind) -> save, fwd, (bwd, side) per setting: the figures of the library BEFORE the arenas were bounded (commit c468c91, library defaults)
+_BLK_SIZES = {
+    (2, 8, 8, 64, 8, 512, 0): (302592, 6628096, ((4867584, 12034816), (4343296, 14656256), (67072, 6791936))),
+    (3, 12, 20, 64, 8, 512, 0): (1679616, 6953984, ((5474560, 13251584), (4950272, 15873024), (370944, 7875584))),
+    (3, 12, 20, 128, 8, 1024, 0): (6308352, 7415552, ((4935424, 25697024), (4935424, 29891328), (741120, 9258752))),
+    (3, 12, 20, 320, 8, 1280, 0): (15844608, 9168896, ((18788608, 54452736), (18788608, 64938496), (8302848, 18384896))),
+    (3, 12, 20, 512, 8, 2048, 0): (25491456, 11475200, ((40383232, 93366528), (40383232, 110143744), (23606016, 26220800))),
+    (2, 16, 16, 192, 3, 768, 1): (5914112, 256, ((8666624, 6698752), (8666624, 6698752), (8669696, 3145984))),
+    (2, 16, 16, 384, 6, 1536, 1): (11820032, 256, ((21264896, 20475136), (21264896, 20475136), (21271040, 6291712))),
+}
+
+
+def _block_entry_bytes(lib, d, G, with_side):
+    import ctypes as C
+    side = C.c_size_t(0)
+    return lib.mdvit_block_bwd_ws_bytes(C.byref(d), C.byref(G), with_side, C.byref(side)), side.value
+
+
+def test_block_entry_sizes_without_gpu():
+    """mdvit_block_save_bytes / _fwd_ws_bytes / _bwd_ws_bytes are the passes themselves run on planning arenas (csrc/block.hip): host logic, no GPU.  Pinned to the
+    figures the library gave before its arenas were bounded -- the layout did not move -- with ONE difference: the DeiT Block_adapt (attn_kind 1) writes its LayerNorm-1
+    data gradient into a slot of the side arena when the caller wants no input gradient, and the planning pass, which cannot see dx, never counted that slot (the
+    kernel then wrote T x C floats past the buffer).  The slot is now taken in every pass, the data-gradient-only one included: side grows by align256(4 T C) in all
+    three settings of attn_kind 1 and nothing else changes."""
+    import ctypes as C
+    from mdvit_amd import _lib
+    lib = _lib.load()
+    for geo, (save, fwd, bwd) in _BLK_SIZES.items():
+        B, H, W, Cn, _heads, _hidden, kind = geo
+        d = _block_entry_desc(*geo)
+        grow = (4 * B * H * W * Cn + 255) // 256 * 256 if kind == 1 else 0
+        assert grow == {0: 0, 1: {192: 393216, 384: 786432}.get(Cn)}[kind]
+        assert lib.mdvit_block_save_bytes(C.byref(d)) == save, geo
+        assert lib.mdvit_block_fwd_ws_bytes(C.byref(d)) == fwd, geo
+        for (acc, dgrad_only, with_side), (ws, side) in zip(_BLK_SETTINGS, bwd):
+            assert _block_entry_bytes(lib, d, _block_entry_grads(acc, dgrad_only), with_side) == (ws, side + grow), (geo, acc, dgrad_only, with_side)
+
+
+@pytest.mark.parametrize("geo", [(3, 12, 20, 128, 8, 1024, 0), (2, 16, 16, 192, 3, 768, 1)])
+def test_block_entry_refuses_short_buffers_without_gpu(geo):
+    """a save buffer, workspace or side workspace ONE byte short of what the *_bytes entries report is refused with MDVIT_E_WORKSPACE before anything is enqueued (the
+    checks precede every HIP call, so this runs without a GPU: a pass that got through would fail with MDVIT_E_HIP here)"""
+    import ctypes as C
+    from mdvit_amd import _lib
+    lib = _lib.load()
+    E_WORKSPACE, p = 4, _BLK_PTR
+    d = _block_entry_desc(*geo)
+    save, fwd = lib.mdvit_block_save_bytes(C.byref(d)), lib.mdvit_block_fwd_ws_bytes(C.byref(d))
+    for sb, wb in ((save - 1, fwd), (save, fwd - 1)):
+        assert lib.mdvit_block_fwd(C.byref(d), p, p, p, sb, p, wb, None) == E_WORKSPACE, (sb, wb)
+        assert b"too small" in lib.mdvit_last_error()
+    for acc, dgrad_only, with_side in _BLK_SETTINGS:
+        G = _block_entry_grads(acc, dgrad_only)
+        st = _lib.BlockStreams()
+        st.main, st.side = None, (p if with_side else None)
+        ws, side = _block_entry_bytes(lib, d, G, with_side)
+        assert ws > 256 and side > 256
+        for sb, wb, sdb in ((save - 1, ws, side), (save, ws - 1, side), (save, ws, side - 1)):
+            assert lib.mdvit_block_bwd(C.byref(d), C.byref(G), C.byref(st), p, p, sb, p, p, p, wb, p, sdb) == E_WORKSPACE, (acc, dgrad_only, with_side, sb, wb, sdb)
+            assert b"too small" in lib.mdvit_last_error()
+
+
 def test_ctypes_mirrors_have_the_layout_of_the_public_header(tmp_path):
     """include/mdvit_hip.h is plain C: compile it with gcc and compare sizeof and every field offset of the five ABI structs with their ctypes mirrors in
     mdvit_amd/_lib.py -- a field added on one side only (this round: a_bf16 / b_bf16, store_bf16, ln_accumulate, the plane pointers) would otherwise
