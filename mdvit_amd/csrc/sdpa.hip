@@ -11,7 +11,7 @@
 // of size [N, N] ever leaves the registers: the forward keeps only the row log-sum-exp, the backward recomputes the probabilities.
 //   forward : S^T tiles (8 x 32 MFMAs per 32 queries) -> softmax -> O = P V (256 MFMAs)            out = a * O, lse
 //   backward: prep   delta[q] = sum_d g out (= rowsum(dO * O)),  e[c] = sum_n g out (the adapter's gradient carrier)
-//             rows   per 32 queries and key tile: S^T, dP^T = V dO^T, dS = P (dP - delta) / 8  ->  dQ += dS K
+//             rows   per 32 queries: S^T, dP^T = V dO^T of all key tiles, delta' = sum_n P dP / sum_n P, dS = P (dP - delta') / 8  ->  dQ += dS K
 //             keys   per 32 keys and query tile:  S = Q K^T, dP = dO V^T, P, dS                 ->  dV += P^T dO, dK += dS^T Q
 #include "common.h"
 
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void sdpa_prep_kernel(const float* __restrict_
 }
 
 __global__ __launch_bounds__(256) void sdpa_mfma_bwd_rows_kernel(const float* __restrict__ g, const float* __restrict__ qkv, const float* __restrict__ lse,
-                                                                 const float* __restrict__ delta, const float* __restrict__ e_part, const float* __restrict__ a,
+                                                                 const float* __restrict__ e_part, const float* __restrict__ a,
                                                                  float* __restrict__ dqkv, float* __restrict__ e, int C, int heads, float scale) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Kt = smem; float* Vt = smem + SD * SLD;
@@ -185,30 +185,62 @@ __global__ __launch_bounds__(256) void sdpa_mfma_bwd_rows_kernel(const float* __
                 df[4 * i] *= av.x; df[4 * i + 1] *= av.y; df[4 * i + 2] *= av.z; df[4 * i + 3] *= av.w;
             }
         }
-        const float l = lse[((long)b * heads + h) * SN + q], dl = delta[((long)b * heads + h) * SN + q];
+        const float l = lse[((long)b * heads + h) * SN + q];
+        // S^T and dP^T of all eight key tiles stay in registers (256 of them: this workgroup's LDS leaves room for one wave per SIMD anyway), so that the row's
+        // delta = sum_n P dP / sum_n P is taken from the SAME recomputed P and dP that form dS.  Then sum_n dS_n = 0 to round-off, as in softmax's textbook backward;
+        // with the prep pass's delta = sum_d g out (another summation of the same number, rounded on its own) the residue sum_n dS_n ~ 1e-7 |dP| met the largest key
+        // in dQ = dS K: rows whose softmax leans on one large key came out 6 to 10 x further off than the textbook form (tests/test_gpu_transfuse_kernels.py).
+        // (the two lane-dependent LDS offsets are made opaque: every operand address below is base + an immediate.  Left to itself the compiler forms the ~300
+        // addresses of the unrolled tiles ahead of the query loop and spills them)
+        int ocol = 32 * lhi * SLD + l31, orow = l31 * SLD + 4 * lhi;
+        asm volatile("" : "+v"(ocol), "+v"(orow));
+        const float* kcol = Kt + ocol; const float* vcol = Vt + ocol;
+        const float* krow0 = Kt + orow; const float* krow1 = Kt + 32 * SLD + orow;
+        f32x16 st[8], dp[8];
+#pragma unroll
+        for (int kt = 0; kt < 8; ++kt) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { st[kt][r] = 0.f; dp[kt][r] = 0.f; }
+#pragma unroll
+            for (int s = 0; s < 32; ++s) {
+                st[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kcol[s * SLD + kt * 32], qf[s], st[kt], 0, 0, 0);
+                dp[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vcol[s * SLD + kt * 32], df[s], dp[kt], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        float num[8], den[8];          // per key tile, this lane's 16 keys; folded pairwise below (fixed order)
+#pragma unroll
+        for (int kt = 0; kt < 8; ++kt) {
+            num[kt] = 0.f; den[kt] = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = __expf(st[kt][r] * scale - l);
+                st[kt][r] = p;
+                num[kt] = fmaf(p, dp[kt][r], num[kt]);
+                den[kt] += p;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        float nsum = ((num[0] + num[1]) + (num[2] + num[3])) + ((num[4] + num[5]) + (num[6] + num[7]));
+        float dsum = ((den[0] + den[1]) + (den[2] + den[3])) + ((den[4] + den[5]) + (den[6] + den[7]));
+        nsum += __shfl_xor(nsum, 32);          // the query's other 128 keys
+        dsum += __shfl_xor(dsum, 32);
+        const float dl = nsum / dsum;
         f32x16 dq[2];
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
-#pragma unroll 1
+#pragma unroll
         for (int kt = 0; kt < 8; ++kt) {
-            f32x16 st, dp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { st[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-            for (int s = 0; s < 32; ++s) {
-                st = __builtin_amdgcn_mfma_f32_32x32x2f32(Kt[(32 * lhi + s) * SLD + kt * 32 + l31], qf[s], st, 0, 0, 0);
-                dp = __builtin_amdgcn_mfma_f32_32x32x2f32(Vt[(32 * lhi + s) * SLD + kt * 32 + l31], df[s], dp, 0, 0, 0);
-            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float p = __expf(st[r] * scale - l);
-                const float ds = p * (dp[r] - dl) * scale;
-                const int key = kt * 32 + drow(r, lhi);
-                dq[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ds, Kt[l31 * SLD + key], dq[0], 0, 0, 0);
-                dq[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ds, Kt[(32 + l31) * SLD + key], dq[1], 0, 0, 0);
+                const float ds = st[kt][r] * (dp[kt][r] - dl) * scale;
+                const int key = kt * 32 + drow(r, 0);          // (+ 4 * lhi: in the bases)
+                dq[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ds, krow0[key], dq[0], 0, 0, 0);
+                dq[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ds, krow1[key], dq[1], 0, 0, 0);
             }
+            __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
@@ -313,7 +345,7 @@ extern "C" int mdvit_sdpa_mfma_bwd(const float* g, const float* qkv, const float
     if (rc != MDVIT_OK) return rc;
     float* e_part = delta + (long)B * heads * N;
     hipLaunchKernelGGL(sdpa_prep_kernel, dim3(B, 4), dim3(256), 0, s, g, out, delta, e_part, C, heads);
-    hipLaunchKernelGGL(sdpa_mfma_bwd_rows_kernel, dim3(heads, B), dim3(256), SMEM_BYTES, s, g, qkv, lse, delta, e_part, a, dqkv, e, C, heads, 0.125f);
+    hipLaunchKernelGGL(sdpa_mfma_bwd_rows_kernel, dim3(heads, B), dim3(256), SMEM_BYTES, s, g, qkv, lse, e_part, a, dqkv, e, C, heads, 0.125f);
     hipLaunchKernelGGL(sdpa_mfma_bwd_keys_kernel, dim3(heads, B), dim3(256), SMEM_BYTES, s, g, qkv, lse, delta, a, dqkv, C, heads, 0.125f);
     MDVIT_LAUNCH_CHECK();
     return MDVIT_OK;
