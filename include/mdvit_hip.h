@@ -802,6 +802,39 @@ int mdvit_se_adapter_fwd(const MdvitSeAdapterDesc* d, const float* x, float* y, 
 int mdvit_se_adapter_bwd(const MdvitSeAdapterDesc* d, const float* g, const float* x, const float* save, float* dx, float* dW1, float* db1, float* dW2,
                          float* db2, float* dWg, float* dbg, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- shifted-window attention of SwinUnet (Models/Transformer/SwinUnet.py:108-139, :227-258; csrc/winattn.hip) ----------------------------------
+ * 8 x 8 windows (64 tokens), head dimension 32, on the fp32 matrix cores.  qkv [B, H*W, 3C] (q|k|v, channel = head * 32 + d) and out [B, H*W, C]
+ * are in NATURAL token order: the cyclic shift (shift = 0 or 4) and both window rearrangements are addressing, the shift mask (-100 between the
+ * regions of the rolled image) is derived from the coordinates, and nothing of size [64, 64] goes to memory.  Per window and head
+ *     S = (q 32^-0.5) k^T + table[index(i, j), head] + mask(i, j),  out = softmax_j(S) v,    table [225, heads], index = (iy-jy+7) * 15 + (ix-jx+7).
+ * lse [B, heads, H*W]: the row log-sum-exp, kept for the backward, which recomputes the probabilities.
+ * Backward: dqkv in qkv's layout (every element written), dtable [225, heads] summed over samples, windows and pairs in a fixed order (per-workgroup
+ * partial rows in ws, mdvit_winattn_bwd_ws_bytes bytes, then a second stage: no atomics, two calls agree bit for bit); accumulate != 0 adds into
+ * dtable; dtable == NULL: data gradient only (ws unused); dqkv == NULL: the table gradient only.
+ * MDVIT_E_SHAPE before any launch: H or W no multiple of 8, C != heads * 32, shift outside {0, 4}, shift != 0 with H == 8 or W == 8. */
+int mdvit_winattn_fwd(const float* qkv, const float* table, float* out, float* lse, int32_t B, int32_t H, int32_t W, int32_t C, int32_t heads,
+                      int32_t shift, void* stream);
+size_t mdvit_winattn_bwd_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t heads);
+int mdvit_winattn_bwd(const float* g, const float* qkv, const float* table, const float* lse, float* dqkv, float* dtable, void* ws, size_t ws_bytes,
+                      int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t C, int32_t heads, int32_t shift, void* stream);
+
+/* ---- LayerNorm with SwinUnet's patch rearrangements in its addressing (csrc/swin_norm.hip): the rearranged tensor is never materialised -------------
+ * merge  (PatchMerging, SwinUnet.py:311-320):  x [B,H,W,C] -> y [B,H/2,W/2,4C] = LN_4C(cat(x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2])); H, W even, 4C <= 1536.
+ * expand (PatchExpand / FinalPatchExpand_X4, :343-350 / :366-373):  u [B,H,W,p p c] -> y [B,pH,pW,c], y[b, h p + p1, w p + p2, :] = LN_c(u[b,h,w,(p1 p + p2) c ...]);
+ *        p = 2 / 4, c <= 1536.
+ * mean / rstd: one per normalised row (B H W / 4, resp. B H W p p), kept for the backward.  Backward: dx / du scattered back to the source layout; dgamma / dbeta
+ * (together, or both NULL: data gradient only, ws unused) by one partial row per workgroup and a fixed-order second stage -- ws: mdvit_partials_ws_bytes(2 L) bytes,
+ * L = 4C resp. c; accumulate != 0 adds into them.  dx / du == NULL: the parameter gradients only.  Two calls agree bit for bit. */
+int mdvit_patch_merge_ln_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int32_t B, int32_t H, int32_t W,
+                             int32_t C, float eps, void* stream);
+int mdvit_patch_merge_ln_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, float* dx, float* dgamma,
+                             float* dbeta, void* ws, size_t ws_bytes, int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t C, void* stream);
+int mdvit_patch_expand_ln_fwd(const float* u, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int32_t B, int32_t H, int32_t W,
+                              int32_t p, int32_t c, float eps, void* stream);
+int mdvit_patch_expand_ln_bwd(const float* dy, const float* u, const float* gamma, const float* mean, const float* rstd, float* du, float* dgamma,
+                              float* dbeta, void* ws, size_t ws_bytes, int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t p, int32_t c,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@ nn.Module call surface.  See DESIGN.md / INTEGRATION.md."""
 from .model import BASE, BASE_DASE, BASE_DSN, BASE_USE, MDViT, MDViT_DSN  # noqa: F401
 from .losses import domain_losses, seg_loss  # noqa: F401
 from .evaluate import EvalAccumulator, evaluate  # noqa: F401
+from .swin import SwinUnet  # noqa: F401
 
 
 def load_reference_state_dict(model, state_dict, strict: bool = True):
@@ -13,5 +14,5 @@ def load_reference_state_dict(model, state_dict, strict: bool = True):
     return model.load_state_dict(sd, strict=strict)
 
 
-__all__ = ["MDViT", "MDViT_DSN", "BASE", "BASE_DSN", "BASE_DASE", "BASE_USE", "domain_losses", "seg_loss", "load_reference_state_dict",
+__all__ = ["MDViT", "MDViT_DSN", "BASE", "BASE_DSN", "BASE_DASE", "BASE_USE", "SwinUnet", "domain_losses", "seg_loss", "load_reference_state_dict",
            "EvalAccumulator", "evaluate"]

@@ -255,6 +255,12 @@ _SIGS = {
     "mdvit_seg_losses_groups_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, vp],
     "mdvit_se_adapter_fwd": [C.POINTER(SeAdapterDesc), vp, vp, vp, vp, C.c_size_t, vp],
     "mdvit_se_adapter_bwd": [C.POINTER(SeAdapterDesc)] + [vp] * 10 + [vp, C.c_size_t, vp],
+    "mdvit_winattn_fwd": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "mdvit_winattn_bwd": [vp, vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, i32, i32, vp],
+    "mdvit_patch_merge_ln_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    "mdvit_patch_merge_ln_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, vp],
+    "mdvit_patch_expand_ln_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp],
+    "mdvit_patch_expand_ln_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, i32, vp],
 }
 
 _lib = None
@@ -345,6 +351,8 @@ def _attach_prototypes(lib):
     lib.mdvit_se_adapter_ws_bytes.argtypes = [C.POINTER(SeAdapterDesc)]
     lib.mdvit_eval_ws_bytes.restype = C.c_size_t
     lib.mdvit_eval_ws_bytes.argtypes = [i32]
+    lib.mdvit_winattn_bwd_ws_bytes.restype = C.c_size_t
+    lib.mdvit_winattn_bwd_ws_bytes.argtypes = [i32, i32, i32, i32]
     for name, sig in _SIGS.items():
         try:
             fn = getattr(lib, name)

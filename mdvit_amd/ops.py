@@ -2429,6 +2429,109 @@ def rowdot(x, w, b=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# shifted-window attention (SwinUnet.py:108-139 + :227-258; csrc/winattn.hip)
+# ------------------------------------------------------------------------------------------------
+class _WindowAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, table, H, W_, heads, shift):
+        ctx.set_materialize_grads(False)
+        _chk(qkv, table)
+        B, N, C3 = qkv.shape
+        Cn = C3 // 3
+        if N != H * W_ or C3 != 3 * Cn or tuple(table.shape) != (225, heads):
+            raise _lib.MdvitHipError(f"window_attention: qkv [B, H*W, 3C] and table [225, heads] expected (qkv {tuple(qkv.shape)}, table {tuple(table.shape)}, "
+                                     f"H={H} W={W_} heads={heads})")
+        out = _empty((B, N, Cn), device=qkv.device, dtype=torch.float32)
+        lse = _empty((B, heads, N), device=qkv.device, dtype=torch.float32)
+        call("mdvit_winattn_fwd", _p(qkv), _p(table), _p(out), _p(lse), B, H, W_, Cn, heads, shift, _stream())
+        ctx.save_for_backward(qkv, table, lse)
+        ctx.meta = (B, H, W_, Cn, heads, shift)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 6
+        qkv, table, lse = ctx.saved_tensors
+        B, H, W_, Cn, heads, shift = ctx.meta
+        g = _c(g)
+        dqkv = _empty_like(qkv) if ctx.needs_input_grad[0] else None
+        want_t = not _dgrad_only and ctx.needs_input_grad[1]
+        st = _sink_of(table) if (want_t and _side_stream is not None) else None
+        dt = _empty_like(table) if (want_t and st is None) else None
+        if dqkv is None and dt is None and st is None:
+            return (None,) * 6
+        wsb = _lib.load().mdvit_winattn_bwd_ws_bytes(B, H, W_, heads)
+        if dqkv is not None or dt is not None:
+            ws = _empty((wsb // 4,), device=g.device, dtype=torch.float32) if dt is not None else None
+            call("mdvit_winattn_bwd", _p(g), _p(qkv), _p(table), _p(lse), _p(dqkv), _p(dt), _p(ws), wsb if dt is not None else 0, 0, B, H, W_, Cn, heads, shift, _stream())
+        if st is not None:      # table gradient on the side stream, into the gradient bucket
+            with _on_side(g, qkv, lse):
+                ws = _empty((wsb // 4,), device=g.device, dtype=torch.float32)
+                call("mdvit_winattn_bwd", _p(g), _p(qkv), _p(table), _p(lse), None, _p(st), _p(ws), wsb, 1, B, H, W_, Cn, heads, shift, _stream())
+        return dqkv, dt, None, None, None, None
+
+
+class _PatchLN(torch.autograd.Function):
+    """LayerNorm with SwinUnet's patch rearrangement in its addressing (csrc/swin_norm.hip).  kind "merge": x [B,H,W,C] -> [B,H/2,W/2,4C];
+    kind "expand": u [B,H,W,p*p*c] -> [B,pH,pW,c]"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, kind, p):
+        ctx.set_materialize_grads(False)
+        _chk(x, gamma, beta)
+        B, H, W_, Cx = x.shape
+        if kind == "merge":
+            Cn, L, oshape, rows = Cx, 4 * Cx, (B, H // 2, W_ // 2, 4 * Cx), B * (H // 2) * (W_ // 2)
+        else:
+            Cn, L, oshape, rows = Cx // (p * p), Cx // (p * p), (B, H * p, W_ * p, Cx // (p * p)), B * H * W_ * p * p
+        if gamma.numel() != L or beta.numel() != L or (kind == "expand" and Cx != p * p * Cn):
+            raise _lib.MdvitHipError(f"patch_{kind}_ln: x {tuple(x.shape)} wants {L} LayerNorm parameters (got {gamma.numel()})")
+        y = _empty(oshape, device=x.device, dtype=torch.float32)
+        mean = _empty((rows,), device=x.device, dtype=torch.float32)
+        rstd = _empty_like(mean)
+        geo = (B, H, W_, Cn) if kind == "merge" else (B, H, W_, p, Cn)
+        call(f"mdvit_patch_{kind}_ln_fwd", _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), *geo, eps, _stream())
+        ctx.save_for_backward(x, gamma, mean, rstd)
+        ctx.meta = (kind, geo, L)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 6
+        x, gamma, mean, rstd = ctx.saved_tensors
+        kind, geo, L = ctx.meta
+        g = _c(g)
+        dx = _empty_like(x) if ctx.needs_input_grad[0] else None
+        if _dgrad_only:          # the aux sweep: no parameter gradients -> no partial sums, no reduction launch
+            if dx is not None:
+                call(f"mdvit_patch_{kind}_ln_bwd", _p(g), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), None, None, None, 0, 0, *geo, _stream())
+            return dx, None, None, None, None, None
+        dg, db = _flat_like(gamma, gamma)
+        wsp, wsb, _keep = _partials_ws(2 * L, x.device)
+        call(f"mdvit_patch_{kind}_ln_bwd", _p(g), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), wsp, wsb, 0, *geo, _stream())
+        return dx, dg, db, None, None, None
+
+
+def patch_merge_ln(x, gamma, beta, eps=1e-5):
+    """PatchMerging's gather + LayerNorm (SwinUnet.py:311-320): x [B,H,W,C] -> LN_4C(cat(x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2])) [B,H/2,W/2,4C]"""
+    return _PatchLN.apply(_c(x), _c(gamma), _c(beta), float(eps), "merge", 2)
+
+
+def patch_expand_ln(u, gamma, beta, p, eps=1e-5):
+    """PatchExpand's / FinalPatchExpand_X4's rearrangement + LayerNorm (SwinUnet.py:343-350, :366-373): u [B,H,W,p*p*c] -> [B,pH,pW,c],
+    'b h w (p1 p2 c) -> b (h p1) (w p2) c' then LN_c"""
+    return _PatchLN.apply(_c(u), _c(gamma), _c(beta), float(eps), "expand", int(p))
+
+
+def window_attention(qkv, table, H, W, heads, shift=0):
+    """qkv [B, H*W, 3 * heads * 32] in natural token order, table [225, heads] -> [B, H*W, heads * 32]: multi-head attention inside 8 x 8 windows of the H x W token
+    grid rolled by `shift` (0 or 4) with the relative-position bias and the shift mask, un-rolled again -- one kernel each way, no rearranged copy."""
+    return _WindowAttention.apply(_c(qkv), _c(table), int(H), int(W), int(heads), int(shift))
+
+
+# ------------------------------------------------------------------------------------------------
 # Squeeze-excite adapters (BASE_DASE / BASE_USE, base_sota_adapt.py:273-637; csrc/se_adapter.hip)
 SE_KINDS = {"dase": _lib.SE_DASE, "use": _lib.SE_USE}
 
