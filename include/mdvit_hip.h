@@ -835,6 +835,29 @@ int mdvit_patch_expand_ln_bwd(const float* dy, const float* u, const float* gamm
                               float* dbeta, void* ws, size_t ws_bytes, int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t p, int32_t c,
                               void* stream);
 
+/* ---- low-rank attention of UTNet (Models/Hybrid_models/UTNetFolder/conv_trans_utils.py:180-215, :247-282, :344-379; csrc/lowrank_attn.hip) -----------------
+ * Every query of an Hq x Wq map attends to the 64 keys of the map reduced to 8 x 8, on the fp32 matrix cores.  Per image and head
+ *     S[i, j] = (q_i . k_j + table[index(cell(i), j), head]) * dim_head^-0.5,   out = dropout(softmax_j S) v,
+ * cell(i) = (y / (Hq/8)) * 8 + x / (Wq/8), index the Swin relative index of two positions of the 8 x 8 grid, table [225, heads].  Heads are INTERLEAVED:
+ * the channel of head h, component d is d * heads + h.  q [B, Hq*Wq, heads*dim_head] with row stride ldq floats (it may be a column slice of a wider product);
+ * k, v [B, 64, heads*dim_head] with row stride ldkv (the two halves of one [B, 64, 2C] product); out [B, Hq*Wq, C] and g contiguous.  lse [B, heads, Hq*Wq]
+ * is all the forward keeps; the backward recomputes the probabilities and re-derives the dropout mask (drop_p, key0, key1, drop_seed as mdvit_dropout_f32).
+ * Nothing of size [Hq*Wq, 64] goes to memory in either direction.
+ * Backward: dq (row stride lddq), dk, dv (row stride lddkv), every element written; dtable [225, heads] summed over images, queries and pairs.  All sums over
+ * queries go through per-workgroup partial rows in ws (mdvit_lrattn_bwd_ws_bytes bytes) and a fixed-order second stage: no atomics, two calls agree bit for
+ * bit.  accumulate != 0 adds into dtable; dtable == NULL: data gradient only; dq == dk == dv == NULL: the table gradient only.
+ * MDVIT_E_SHAPE before any launch: Hq or Wq no multiple of 8, dim_head outside {16, 32, 64, 128}; MDVIT_E_WORKSPACE: ws too small. */
+int mdvit_lrattn_fwd(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const float* table, float* out, float* lse, int32_t B, int32_t Hq,
+                     int32_t Wq, int32_t dim_head, int32_t heads, float drop_p, uint32_t key0, uint32_t key1, const uint32_t* drop_seed, void* stream);
+size_t mdvit_lrattn_bwd_ws_bytes(int32_t B, int32_t Hq, int32_t Wq, int32_t dim_head, int32_t heads);
+int mdvit_lrattn_bwd(const float* g, const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const float* table, const float* lse, float* dq,
+                     int64_t lddq, float* dk, float* dv, int64_t lddkv, float* dtable, void* ws, size_t ws_bytes, int32_t accumulate, int32_t B, int32_t Hq,
+                     int32_t Wq, int32_t dim_head, int32_t heads, float drop_p, uint32_t key0, uint32_t key1, const uint32_t* drop_seed, void* stream);
+
+/* nn.MaxPool2d(2), NHWC, H and W even (csrc/pool.hip); idx: uint8 winning tap per output element, the first maximum in row-major order on ties (as ATen) */
+int mdvit_maxpool2x2_fwd(const float* x, float* y, void* idx, int32_t B, int32_t H, int32_t W, int32_t C, void* stream);
+int mdvit_maxpool2x2_bwd(const float* dy, const void* idx, float* dx, int32_t B, int32_t H, int32_t W, int32_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ from .model import BASE, BASE_DASE, BASE_DSN, BASE_USE, MDViT, MDViT_DSN  # noqa
 from .losses import domain_losses, seg_loss  # noqa: F401
 from .evaluate import EvalAccumulator, evaluate  # noqa: F401
 from .swin import SwinUnet  # noqa: F401
+from .utnet import UTNet  # noqa: F401
 
 
 def load_reference_state_dict(model, state_dict, strict: bool = True):
@@ -14,5 +15,5 @@ def load_reference_state_dict(model, state_dict, strict: bool = True):
     return model.load_state_dict(sd, strict=strict)
 
 
-__all__ = ["MDViT", "MDViT_DSN", "BASE", "BASE_DSN", "BASE_DASE", "BASE_USE", "SwinUnet", "domain_losses", "seg_loss", "load_reference_state_dict",
+__all__ = ["MDViT", "MDViT_DSN", "BASE", "BASE_DSN", "BASE_DASE", "BASE_USE", "SwinUnet", "UTNet", "domain_losses", "seg_loss", "load_reference_state_dict",
            "EvalAccumulator", "evaluate"]

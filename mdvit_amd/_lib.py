@@ -257,6 +257,10 @@ _SIGS = {
     "mdvit_se_adapter_bwd": [C.POINTER(SeAdapterDesc)] + [vp] * 10 + [vp, C.c_size_t, vp],
     "mdvit_winattn_fwd": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "mdvit_winattn_bwd": [vp, vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, i32, i32, vp],
+    "mdvit_lrattn_fwd": [vp, i64, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, f32, u32, u32, vp, vp],
+    "mdvit_lrattn_bwd": [vp, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, i32, f32, u32, u32, vp, vp],
+    "mdvit_maxpool2x2_fwd": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "mdvit_maxpool2x2_bwd": [vp, vp, vp, i32, i32, i32, i32, vp],
     "mdvit_patch_merge_ln_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
     "mdvit_patch_merge_ln_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, vp],
     "mdvit_patch_expand_ln_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp],
@@ -353,6 +357,8 @@ def _attach_prototypes(lib):
     lib.mdvit_eval_ws_bytes.argtypes = [i32]
     lib.mdvit_winattn_bwd_ws_bytes.restype = C.c_size_t
     lib.mdvit_winattn_bwd_ws_bytes.argtypes = [i32, i32, i32, i32]
+    lib.mdvit_lrattn_bwd_ws_bytes.restype = C.c_size_t
+    lib.mdvit_lrattn_bwd_ws_bytes.argtypes = [i32, i32, i32, i32, i32]
     for name, sig in _SIGS.items():
         try:
             fn = getattr(lib, name)

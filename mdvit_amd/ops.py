@@ -2532,6 +2532,293 @@ def window_attention(qkv, table, H, W, heads, shift=0):
 
 
 # ------------------------------------------------------------------------------------------------
+# UTNet's operators (Models/Hybrid_models/UTNetFolder): low-rank attention (csrc/lowrank_attn.hip), MaxPool2d(2) (csrc/pool.hip),
+# align_corners=True resize to a given size, and the small tape helpers the model needs
+# ------------------------------------------------------------------------------------------------
+class _LowrankAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, table, Hq, Wq, heads, drop_p, key):
+        ctx.set_materialize_grads(False)
+        _chk(table)
+        if not all(t.is_cuda and t.dtype == torch.float32 and t.data_ptr() % 4 == 0 for t in (q, k, v)):
+            raise _lib.MdvitHipError("lowrank_attention: fp32 CUDA(HIP) tensors expected; there is no CPU path")
+        if q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or q.stride(2) != 1 or k.stride(2) != 1 or v.stride(2) != 1:
+            raise _lib.MdvitHipError("lowrank_attention: q [B, N, C], k and v [B, 64, C] with contiguous rows expected")
+        B, N, Cn = q.shape
+        D = Cn // heads
+        ok_q = N == Hq * Wq and q.stride(0) == N * q.stride(1)
+        ok_kv = tuple(k.shape) == (B, 64, Cn) and tuple(v.shape) == (B, 64, Cn) and k.stride() == v.stride() and k.stride(0) == 64 * k.stride(1)
+        if not ok_q or not ok_kv or Cn != D * heads or tuple(table.shape) != (225, heads):
+            raise _lib.MdvitHipError(f"lowrank_attention: q [B, Hq*Wq, C] (rows evenly strided), k and v [B, 64, C] of one stride, table [225, heads] expected "
+                                     f"(q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, table {tuple(table.shape)}, Hq={Hq} Wq={Wq} heads={heads})")
+        out = _empty((B, N, Cn), device=q.device, dtype=torch.float32)
+        lse = _empty((B, heads, N), device=q.device, dtype=torch.float32)
+        seed = _seed_ptr() if drop_p > 0 else None
+        call("mdvit_lrattn_fwd", _p(q), q.stride(1), _p(k), _p(v), k.stride(1), _p(table), _p(out), _p(lse), B, Hq, Wq, D, heads, drop_p, key[0], key[1], seed, _stream())
+        ctx.save_for_backward(q, k, v, table, lse)
+        ctx.meta = (B, Hq, Wq, D, heads, drop_p, key)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 9
+        q, k, v, table, lse = ctx.saved_tensors
+        B, Hq, Wq, D, heads, drop_p, key = ctx.meta
+        g = _c(g)
+        Cn = D * heads
+        data = any(ctx.needs_input_grad[:3])
+        want_t = not _dgrad_only and ctx.needs_input_grad[3]
+        st = _sink_of(table) if (want_t and _side_stream is not None) else None
+        dt = _empty_like(table) if (want_t and st is None) else None
+        if not data and dt is None and st is None:
+            return (None,) * 9
+        dq = dk = dv = None
+        wsb = _lib.load().mdvit_lrattn_bwd_ws_bytes(B, Hq, Wq, D, heads)
+        seed = _seed_ptr() if drop_p > 0 else None
+        geo = (B, Hq, Wq, D, heads, drop_p, key[0], key[1], seed)
+        if data or dt is not None:
+            if data:
+                dq = _empty((B, Hq * Wq, Cn), device=g.device, dtype=torch.float32)
+                dk = _empty((B, 64, Cn), device=g.device, dtype=torch.float32)
+                dv = _empty_like(dk)
+            ws = _empty((wsb // 4,), device=g.device, dtype=torch.float32)
+            call("mdvit_lrattn_bwd", _p(g), _p(q), q.stride(1), _p(k), _p(v), k.stride(1), _p(table), _p(lse), _p(dq), Cn, _p(dk), _p(dv), Cn, _p(dt), _p(ws), wsb, 0,
+                 *geo, _stream())
+        if st is not None:      # table gradient on the side stream, into the gradient bucket
+            with _on_side(g, q, k, v, lse):
+                ws = _empty((wsb // 4,), device=g.device, dtype=torch.float32)
+                call("mdvit_lrattn_bwd", _p(g), _p(q), q.stride(1), _p(k), _p(v), k.stride(1), _p(table), _p(lse), None, Cn, None, None, Cn, _p(st), _p(ws), wsb, 1,
+                     *geo, _stream())
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None), (dk if need[1] else None), (dv if need[2] else None), dt, None, None, None, None, None
+
+
+def lowrank_attention(q, k, v, table, Hq, Wq, heads, drop_p: float = 0.0, key=None, training: bool = True):
+    """UTNet's attention: q [B, Hq*Wq, heads*D] (may be a column slice of a wider product), k and v [B, 64, heads*D] (may be the two halves of one [B, 64, 2C]
+    product), table [225, heads] -> [B, Hq*Wq, heads*D].  Heads interleaved (channel = d * heads + h), D in {16, 32, 64, 128}; the relative-position bias is
+    indexed by the query's coarse cell and added before the scale; dropout (drop_p, training) acts on the probabilities, its mask re-derived from `key`
+    (default: the next key of the package's counter) in the backward.  One kernel forward, one plus two small fixed-order reductions backward."""
+    p = float(drop_p) if training else 0.0
+    if p > 0.0 and key is None:
+        key = _next_key()
+    return _LowrankAttention.apply(q, k, v, _c(table), int(Hq), int(Wq), int(heads), p, tuple(int(x) for x in key) if p > 0.0 else (0, 0))
+
+
+class _MaxPool2x2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.set_materialize_grads(False)
+        _chk(x)
+        B, H, W_, Cn = x.shape
+        y = _empty((B, H // 2, W_ // 2, Cn), device=x.device, dtype=torch.float32)
+        idx = torch.empty(y.shape, device=x.device, dtype=torch.uint8)
+        call("mdvit_maxpool2x2_fwd", _p(x), _p(y), C.c_void_p(idx.data_ptr()), B, H, W_, Cn, _stream())
+        ctx.save_for_backward(idx)
+        ctx.shape = (B, H, W_, Cn)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None
+        (idx,) = ctx.saved_tensors
+        B, H, W_, Cn = ctx.shape
+        dx = _empty(ctx.shape, device=g.device, dtype=torch.float32)
+        call("mdvit_maxpool2x2_bwd", _p(_c(g)), C.c_void_p(idx.data_ptr()), _p(dx), B, H, W_, Cn, _stream())
+        return dx
+
+
+def maxpool2x2(x):
+    """nn.MaxPool2d(2) on NHWC [B, H, W, C], H and W even; ties go to the first maximum in row-major order"""
+    return _MaxPool2x2.apply(_c(x))
+
+
+class _ResizeTo(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, Ho, Wo):
+        ctx.set_materialize_grads(False)
+        _chk(x)
+        B, H, W_, Cn = x.shape
+        y = _empty((B, Ho, Wo, Cn), device=x.device, dtype=torch.float32)
+        call("mdvit_resize_ac_fwd", _p(x), _p(y), B, H, W_, Ho, Wo, Cn, _stream())
+        ctx.meta = (B, H, W_, Ho, Wo, Cn)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        B, H, W_, Ho, Wo, Cn = ctx.meta
+        dx = _empty((B, H, W_, Cn), device=g.device, dtype=torch.float32)
+        call("mdvit_resize_ac_bwd", _p(_c(g)), _p(dx), B, H, W_, Ho, Wo, Cn, _stream())
+        return dx, None, None
+
+
+def resize_ac_to(x, Ho, Wo):
+    """F.interpolate(mode='bilinear', align_corners=True) of NHWC [B, H, W, C] to Ho x Wo, up or down"""
+    return _ResizeTo.apply(_c(x), int(Ho), int(Wo))
+
+
+class _Add(torch.autograd.Function):
+    """a + b as a kernel of this package (an identity shortcut); both sources get the SAME gradient tensor"""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        ctx.set_materialize_grads(False)
+        _chk(a, b)
+        y = _empty_like(a)
+        call("mdvit_ew", _p(a), _p(b), _p(y), a.numel(), 3, _stream())
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, g
+
+
+def add(a, b):
+    return _Add.apply(_c(a), _c(b))
+
+
+class _LinearExact(torch.autograd.Function):
+    """y = x W^T [+ residual] on the fp32-input matrix cores in EVERY GEMM mode, all three products: the few-channel products at the image (K = 4 and 36 in UTNet's
+    first block), whose BatchNorm gradients cancel to 1e-4 of their terms -- the 1e-5 of the bf16x3 split would show there as percents"""
+
+    @staticmethod
+    def forward(ctx, x, W, residual):
+        ctx.set_materialize_grads(False)
+        _chk(x, W, residual)
+        M, K = x.shape
+        N = W.shape[0]
+        y = _empty((M, N), device=x.device, dtype=torch.float32)
+        gemm(_p(x), _p(W), _p(y), M, N, K, lda=K, ldb=K, ldc=N, residual=_p(residual), ldr=N, allow_split=True, precision=0)
+        ctx.save_for_backward(x, W)
+        ctx.has_res = residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        x, W = ctx.saved_tensors
+        g = _c(g)
+        M, K = x.shape
+        N = W.shape[0]
+        dx = dW = None
+        if ctx.needs_input_grad[0]:
+            dx = _empty_like(x)
+            gemm(_p(g), _p(W), _p(dx), M, K, N, lda=N, ldb=K, ldc=K, trans_b=False, allow_split=True, precision=0)
+        if ctx.needs_input_grad[1] and not _dgrad_only:
+            dW = _empty_like(W)
+            gemm(_p(g), _p(x), _p(dW), N, K, M, lda=N, ldb=K, ldc=K, trans_a=True, trans_b=False, allow_split=True, precision=0)
+        return dx, dW, (g if ctx.has_res else None)
+
+
+def linear_exact(x, W, residual=None):
+    """x [..., K] W[N, K]^T (+ residual [..., N]) with exact fp32 products whatever the GEMM mode (see _LinearExact); W.numel() == N * K, any shape"""
+    shp = x.shape
+    N = W.shape[0]
+    y = _LinearExact.apply(_c(x).view(-1, shp[-1]), _c(W).view(N, -1), None if residual is None else _c(residual).view(-1, N))
+    return y.view(*shp[:-1], N)
+
+
+class _Conv3x3Exact(torch.autograd.Function):
+    """dense 3 x 3 convolution (stride 1, padding 1, no bias) with exact fp32 products in EVERY GEMM mode: im2col + the fp32-input matrix cores, all three products.
+    The column matrix is a temporary each way (rebuilt from the saved image in the backward), never kept.  For UTNet's first stage: see _LinearExact."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        ctx.set_materialize_grads(False)
+        _chk(x, w)
+        B, H, W_, Cin = x.shape
+        Cout, K, M = w.shape[0], 9 * Cin, B * H * W_
+        col = _empty((M, K), device=x.device, dtype=torch.float32)
+        call("mdvit_im2col3x3", _p(x), _p(col), B, H, W_, Cin, 1, 1, _stream())
+        y = _empty((B, H, W_, Cout), device=x.device, dtype=torch.float32)
+        gemm(_p(col), _p(w), _p(y), M, Cout, K, lda=K, ldb=K, ldc=Cout, allow_split=True, precision=0)
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None
+        x, w = ctx.saved_tensors
+        g = _c(g)
+        B, H, W_, Cin = x.shape
+        Cout, K, M = w.shape[0], 9 * Cin, B * H * W_
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dcol = _empty((M, K), device=x.device, dtype=torch.float32)
+            gemm(_p(g), _p(w), _p(dcol), M, K, Cout, lda=Cout, ldb=K, ldc=K, trans_b=False, allow_split=True, precision=0)
+            dx = _empty_like(x)
+            call("mdvit_col2im3x3", _p(dcol), _p(dx), B, H, W_, Cin, 1, 1, _stream())
+            del dcol
+        if ctx.needs_input_grad[1] and not _dgrad_only:
+            col = _empty((M, K), device=x.device, dtype=torch.float32)
+            call("mdvit_im2col3x3", _p(x), _p(col), B, H, W_, Cin, 1, 1, _stream())
+            dw = _empty_like(w)
+            gemm(_p(g), _p(col), _p(dw), Cout, K, M, lda=Cout, ldb=K, ldc=K, trans_a=True, trans_b=False, allow_split=True, precision=0)
+        return dx, dw
+
+
+def conv3x3_exact(x, w):
+    """x NHWC [B, H, W, Cin] (Cin % 4 == 0), w [Cout, Cin, 3, 3] contiguous -> [B, H, W, Cout], stride 1, padding 1; exact fp32 products whatever the GEMM mode"""
+    return _Conv3x3Exact.apply(_c(x), _c(w))
+
+
+class _SplitRows(torch.autograd.Function):
+    """W [sum(sizes), K] (a [N, K, 1, 1] convolution weight included) -> row-block views (no copy); the backward concatenates the block gradients once"""
+
+    @staticmethod
+    def forward(ctx, W, sizes):
+        ctx.set_materialize_grads(False)
+        ctx.sizes, ctx.shape = tuple(sizes), tuple(W.shape)
+        W2, out, off = W.view(W.shape[0], -1), [], 0
+        for n in sizes:
+            out.append(W2[off:off + n])
+            off += n
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        if all(g is None for g in gs):
+            return None, None
+        ref = next(g for g in gs if g is not None)
+        parts = [g if g is not None else torch.zeros((n, ref.shape[1]), device=ref.device, dtype=ref.dtype) for g, n in zip(gs, ctx.sizes)]
+        return torch.cat(parts, 0).view(ctx.shape), None
+
+
+def split_rows(W, sizes):
+    assert sum(sizes) == W.shape[0]
+    return _SplitRows.apply(_c(W), tuple(int(n) for n in sizes))
+
+
+class _PadZeros(torch.autograd.Function):
+    """t -> t with dimension `dim` zero-padded to `size` (a 3-channel image's BatchNorm vectors and convolution weights, padded to the 4 channels the NHWC
+    kernels take); the backward hands the leading block back"""
+
+    @staticmethod
+    def forward(ctx, t, dim, size):
+        ctx.set_materialize_grads(False)
+        ctx.meta = (dim, t.shape[dim])
+        shp = list(t.shape)
+        shp[dim] = size - t.shape[dim]
+        return torch.cat([t, torch.zeros(shp, device=t.device, dtype=t.dtype)], dim)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        dim, n = ctx.meta
+        return g.narrow(dim, 0, n).contiguous(), None, None
+
+
+def pad_zeros(t, dim, size):
+    return t if t.shape[dim] == size else _PadZeros.apply(t, int(dim), int(size))
+
+
+# ------------------------------------------------------------------------------------------------
 # Squeeze-excite adapters (BASE_DASE / BASE_USE, base_sota_adapt.py:273-637; csrc/se_adapter.hip)
 SE_KINDS = {"dase": _lib.SE_DASE, "use": _lib.SE_USE}
 
