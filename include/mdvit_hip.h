@@ -693,6 +693,20 @@ int mdvit_augment_normalize_u8(const uint8_t* img_nhwc, const uint8_t* mask, con
  * coordinate (xs, ys) of an H x W image, from the same inline code the kernel compiles.  idx5: linear indices y*W + x of the taps (y0,x0) (y0,x1)
  * (y1,x0) (y1,x1) and of the nearest tap; w4: the four bilinear weights.  Non-finite coordinates give tap 0 with weight 1. */
 int mdvit_augment_probe_taps(float xs, float ys, int32_t H, int32_t W, int32_t* idx5, float* w4);
+/* A batch out of a device-resident dataset, one launch: sample index[b] of the pool, resized to H x W as the loader's A.Resize does it
+ * (create_dataset.py:132-142: cv2.resize with INTER_LINEAR for the image and INTER_NEAREST for the mask).
+ * img_pool [N,Hs,Ws,3] uint8, mask_pool [N,Hs,Ws] uint8 or NULL, index [B] int64 on the device -> img_out [B,H,W,3], mask_out [B,H,W] (NULL with a NULL
+ * mask pool): the layout mdvit_augment_normalize_u8 and mdvit_image_normalize_u8 take.  Integer arithmetic only.  ytab [5][H] and xtab [5][W] int32 on the
+ * device (ytab_len = 5 H, xtab_len = 5 W entries) are planar: s0, s1 = the two source taps of an output position, a0, a1 = their weights in 1/2048,
+ * sn = its nearest tap; mdvit_amd/data.py (resize_table) builds them on the host, where all floating-point work is done once per size.  Per pixel
+ *   t(row) = S[row][s0x] a0x + S[row][s1x] a1x,   dst = (((a0y (t(s0y) >> 4)) >> 16) + ((a1y (t(s1y) >> 4)) >> 16) + 2) >> 2,   mask = M[sny][snx].
+ * Hs == H and Ws == W: a plain gather (the tables are not read).  Sample indices are clamped to [0, N) and taps to the source image, so nothing
+ * reads outside the pool; the caller still validates the index list on the host.  MDVIT_E_SHAPE / MDVIT_E_ALIGN before any launch: a null operand,
+ * a mask pool without a mask output or the reverse, a size < 1, B outside [1, 65535], N < 1 or a pool past 2^40 bytes, a sample past 2^31 - 1 bytes,
+ * tables of another length, a misaligned index list or table.  Offsets into the pool are 64-bit. */
+int mdvit_gather_resize_u8(const uint8_t* img_pool, const uint8_t* mask_pool, const int64_t* index, const int32_t* ytab, int32_t ytab_len,
+                           const int32_t* xtab, int32_t xtab_len, uint8_t* img_out, uint8_t* mask_out, int64_t N, int32_t B, int32_t Hs, int32_t Ws,
+                           int32_t H, int32_t W, void* stream);
 
 /* ---- AdamW over all parameters in one launch (optim.AdamW, multi_train_MDViT.py:91-93) --------------------
  * table_dev: device array [n_tensors][5] of int64 {param, grad, exp_avg, exp_avg_sq (pointers), numel}; every row gets blocks_per_tensor

@@ -246,6 +246,7 @@ _SIGS = {
     "mdvit_image_normalize_u8": [vp, vp, i32, i32, i32, vp],
     "mdvit_augment_normalize_u8": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "mdvit_augment_probe_taps": [f32, f32, i32, i32, C.POINTER(i32), C.POINTER(f32)],
+    "mdvit_gather_resize_u8": [vp, vp, vp, vp, i32, vp, i32, vp, vp, i64, i32, i32, i32, i32, i32, vp],
     "mdvit_seg_losses_sums": [vp, vp, vp, vp, i64, vp],
     "mdvit_seg_losses_final": [vp, vp, i64, i32, vp],
     "mdvit_seg_losses_bwd": [vp, vp, vp, vp, vp, vp, vp, i64, f32, vp],

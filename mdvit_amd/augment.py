@@ -3,7 +3,9 @@
 The reference runs five albumentations transforms per image on the host -- GaussNoise, HorizontalFlip, VerticalFlip, ShiftScaleRotate,
 RandomBrightnessContrast -- then norm01 and Normalize.  Here the random DRAW stays on the host (a few floats per sample, deterministic from a
 torch.Generator) and the APPLICATION is one HIP gather kernel on the uint8 batch (csrc/augment.hip, ops.augment_normalize_u8), which also does the
-normalisation and the label cast.  Resize is taken as done (Datasets/process_resize.py stores the images at size).
+normalisation and the label cast.  The A.Resize(img_size, img_size) in front of the pipeline is NOT done here (the kernel's input and output sizes are equal;
+Datasets/process_resize.py stores 512 x 512 while Configs/multi_train_local.yml trains at 256): mdvit_amd.data.DeviceDataset.batch resizes on the device
+(csrc/dataset.hip) and hands this module a batch at size; a host loader that feeds TrainAug directly keeps its own A.Resize.
 
 The semantics are the published albumentations 1.x defaults, restated (nothing is imported from albumentations; the reference pins no version, so the
 pipeline is parity-unpinned like oracle/pipeline.py):

@@ -83,20 +83,20 @@ __global__ __launch_bounds__(256) void dwconv3x3_dgrad_kernel(const float* __res
 }
 
 // wgrad: dw[c,kh,kw] = sum_{b,ho,wo} dy[b,ho,wo,c] * x[b,ho*s+kh-1,wo*s+kw-1,c]; dbias[c] = sum dy.
-// Block = (C/4 quads) x (256/(C/4) token lanes) over a contiguous chunk of output tokens; register
-// partials -> LDS atomics -> one global atomic per (c,tap) per block.
+// Block = (C/4 quads) x (256/(C/4) token lanes) over a contiguous chunk of output tokens (C <= 1024: every quad has its own threads); register
+// partials -> one LDS row per token lane -> the lanes summed in lane order -> one partial row per block (summed over blocks by mdvit_reduce_partials).
+// No atomics anywhere: the same inputs give the same bits in every run.  LDS: [ntl][10][C] floats, at most 40 KiB.
 __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                               float* __restrict__ part,
                                                               int B, int Hi, int Wi, int C, int stride, int tokens_per_block) {
-    extern __shared__ float s_acc[];   // [C][10]
-    for (int i = threadIdx.x; i < C * 10; i += blockDim.x) s_acc[i] = 0.f;
-    __syncthreads();
+    extern __shared__ float s_part[];   // [ntl][10][C]: tap-major, channel minor (taps 0..8, then the bias)
     const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1, QC = C >> 2;
     const long ntok = (long)B * Ho * Wo;
     const long t_beg = (long)blockIdx.x * tokens_per_block, t_end = min(ntok, t_beg + tokens_per_block);
     const int nquads_blk = min(QC, 256);
     const int tl = threadIdx.x / nquads_blk, ntl = blockDim.x / nquads_blk;
-    for (int q = threadIdx.x % nquads_blk; q < QC; q += nquads_blk) {
+    {
+        const int q = threadIdx.x % nquads_blk;
         const int c = q * 4;
         float4 acc[9];
         float4 accb = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -123,19 +123,20 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __res
                 }
             }
         }
+        if (tl < ntl) {
+            float* mine = s_part + (size_t)tl * 10 * C + c;
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            atomicAdd(&s_acc[(c + 0) * 10 + t], acc[t].x); atomicAdd(&s_acc[(c + 1) * 10 + t], acc[t].y);
-            atomicAdd(&s_acc[(c + 2) * 10 + t], acc[t].z); atomicAdd(&s_acc[(c + 3) * 10 + t], acc[t].w);
+            for (int t = 0; t < 9; ++t) *reinterpret_cast<float4*>(mine + t * C) = acc[t];
+            *reinterpret_cast<float4*>(mine + 9 * C) = accb;
         }
-        atomicAdd(&s_acc[(c + 0) * 10 + 9], accb.x); atomicAdd(&s_acc[(c + 1) * 10 + 9], accb.y);
-        atomicAdd(&s_acc[(c + 2) * 10 + 9], accb.z); atomicAdd(&s_acc[(c + 3) * 10 + 9], accb.w);
     }
     __syncthreads();
     float* row = part + (long)blockIdx.x * C * 10;       // [dw (C*9) | dbias (C)], summed over workgroups by mdvit_reduce_partials
     for (int i = threadIdx.x; i < C * 10; i += blockDim.x) {
-        const int c = i / 10, t = i % 10;
-        row[t < 9 ? c * 9 + t : C * 9 + c] = s_acc[i];
+        const int t = i / C, c = i - t * C;
+        float v = s_part[i];
+        for (int l = 1; l < ntl; ++l) v += s_part[(size_t)l * 10 * C + i];
+        row[t < 9 ? c * 9 + t : C * 9 + c] = v;
     }
 }
 
@@ -1133,7 +1134,8 @@ extern "C" int mdvit_dwconv3x3_bwd(const float* dy, const float* x, const float*
         int tpb = (int)max(64L, (ntok + 1023) / 1024);
         const int nblk = cdiv(ntok, tpb);
         MDVIT_CHECK_PARTIALS_WS(ws, ws_bytes, nblk, 10 * C, "dwconv3x3_bwd");
-        hipLaunchKernelGGL(dwconv3x3_wgrad_kernel, dim3(nblk), dim3(256), sizeof(float) * 10 * C, s, dy, x, (float*)ws, B, Hi, Wi, C, stride, tpb);
+        const int lanes = 256 / (C / 4);                    // token lanes per block (C <= 1024): one LDS row of 10 C floats each, <= 40 KiB in all
+        hipLaunchKernelGGL(dwconv3x3_wgrad_kernel, dim3(nblk), dim3(256), sizeof(float) * 10 * C * lanes, s, dy, x, (float*)ws, B, Hi, Wi, C, stride, tpb);
         const int rc = mdvit_reduce_partials((const float*)ws, nblk, 10L * C, 9 * C, dw, C, dbias, accumulate, s);
         if (rc != MDVIT_OK) return rc;
     }

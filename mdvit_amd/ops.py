@@ -3605,6 +3605,40 @@ def augment_normalize_u8(img_u8_nhwc, mask_u8, params, keys):
     return y, lab
 
 
+def gather_resize_u8(img_pool, mask_pool, index, ytab, xtab, out_img=None, out_mask=None):
+    """A batch out of a device-resident dataset: img_pool uint8 [N,Hs,Ws,3], mask_pool uint8 [N,Hs,Ws] or None, index int64 [B], all on one device, and the
+    int32 tables ytab [5,H] / xtab [5,W] of mdvit_amd.data.resize_table on it -> (uint8 [B,H,W,3], uint8 [B,H,W] or None): the samples the index names,
+    resized as the loader's A.Resize does it (linear for the image, nearest for the mask), one launch of integer arithmetic (csrc/dataset.hip).  Equal sizes
+    are a plain gather.  The index list is the caller's to validate (mdvit_amd.data.DeviceDataset.batch does).  out_img / out_mask: buffers to write into."""
+    if img_pool.dtype != torch.uint8 or img_pool.dim() != 4 or img_pool.shape[-1] != 3 or not img_pool.is_cuda or not img_pool.is_contiguous():
+        raise _lib.MdvitHipError("gather_resize_u8 expects the image pool as a contiguous CUDA uint8 tensor [N,Hs,Ws,3]")
+    N, Hs, Ws, _ = img_pool.shape
+    dev = img_pool.device
+    if mask_pool is not None and (mask_pool.dtype != torch.uint8 or tuple(mask_pool.shape) != (N, Hs, Ws) or mask_pool.device != dev or not mask_pool.is_contiguous()):
+        raise _lib.MdvitHipError(f"gather_resize_u8 expects the mask pool as a contiguous uint8 tensor [{N},{Hs},{Ws}] on the image pool's device")
+    if index.dtype != torch.int64 or index.dim() != 1 or index.device != dev:
+        raise _lib.MdvitHipError("gather_resize_u8 expects the index list as an int64 tensor [B] on the pool's device")
+    for name, tab in (("ytab", ytab), ("xtab", xtab)):
+        if tab.dtype != torch.int32 or tab.dim() != 2 or tab.shape[0] != 5 or tab.device != dev:
+            raise _lib.MdvitHipError(f"gather_resize_u8 expects {name} as an int32 tensor [5,n] on the pool's device")
+    index, ytab, xtab = _c(index), _c(ytab), _c(xtab)
+    B, H, W_ = index.shape[0], ytab.shape[1], xtab.shape[1]
+    if out_img is None:
+        out_img = torch.empty((B, H, W_, 3), device=dev, dtype=torch.uint8)
+    elif out_img.dtype != torch.uint8 or tuple(out_img.shape) != (B, H, W_, 3) or out_img.device != dev or not out_img.is_contiguous():
+        raise _lib.MdvitHipError(f"gather_resize_u8 expects out_img as a contiguous uint8 tensor [{B},{H},{W_},3] on the pool's device")
+    if mask_pool is None:
+        if out_mask is not None:
+            raise _lib.MdvitHipError("gather_resize_u8: out_mask without a mask pool")
+    elif out_mask is None:
+        out_mask = torch.empty((B, H, W_), device=dev, dtype=torch.uint8)
+    elif out_mask.dtype != torch.uint8 or tuple(out_mask.shape) != (B, H, W_) or out_mask.device != dev or not out_mask.is_contiguous():
+        raise _lib.MdvitHipError(f"gather_resize_u8 expects out_mask as a contiguous uint8 tensor [{B},{H},{W_}] on the pool's device")
+    call("mdvit_gather_resize_u8", _p(img_pool), _p(mask_pool), _p(index), _p(ytab), ytab.numel(), _p(xtab), xtab.numel(), _p(out_img), _p(out_mask),
+         N, B, Hs, Ws, H, W_, _stream())
+    return out_img, out_mask
+
+
 # ------------------------------------------------------------------------------------------------
 # a whole backward sweep on a stream of its own
 # ------------------------------------------------------------------------------------------------
