@@ -717,6 +717,23 @@ int mdvit_gather_resize_u8(const uint8_t* img_pool, const uint8_t* mask_pool, co
 int mdvit_adamw_step(const void* table_dev, int32_t n_tensors, int32_t blocks_per_tensor, const float* lr_dev, float* step_dev,
                      float beta1, float beta2, float eps, float weight_decay, int32_t zero_grad, void* stream);
 
+/* The same launch with the decay rule named: mode 0 = decoupled decay (what mdvit_adamw_step runs: it forwards to this instantiation), mode 1 =
+ * torch.optim.Adam (the reference's `train.optimizer.mode: 'adam'`): coupled L2, g <- g + weight_decay * p before the moments, no decoupled decay.
+ * Everything else -- the single-tensor expression, the bias corrections, lr_dev / step_dev, the table and its slicing, zero_grad -- is shared; the
+ * mode is a template parameter of the kernel.  Any other mode is MDVIT_E_SHAPE. */
+int mdvit_adam_step(const void* table_dev, int32_t n_tensors, int32_t blocks_per_tensor, const float* lr_dev, float* step_dev,
+                    float beta1, float beta2, float eps, float weight_decay, int32_t zero_grad, int32_t mode, void* stream);
+
+/* ---- a set of tensors <-> one flat buffer in one launch (csrc/snapshot.hip; mdvit_amd.snapshot.DeviceSnapshot) -----------------------
+ * table_dev: device array [n_rows][3] of int64 {tensor pointer, byte offset in the flat buffer, nbytes}, one row per chunk of a tensor (every row
+ * gets blocks_per_row workgroups; tables of more than 65535 rows go out in slices).  pack copies every tensor's bytes to dst + offset, unpack copies
+ * src + offset back into the tensors; bytes that no row names are not touched on either side.  A row is moved in 16-byte accesses where both of its
+ * sides are 16-byte aligned, in 4-byte words where both are 4-byte aligned, byte by byte otherwise, plus a byte tail.  The flat buffer must be
+ * 16-byte aligned (MDVIT_E_ALIGN); null pointers, n_rows <= 0 and blocks_per_row outside [1, 65535] are MDVIT_E_SHAPE -- all before any launch.
+ * The rows are trusted: the caller keeps pointer + nbytes inside its tensors and offset + nbytes inside the flat buffer. */
+int mdvit_table_pack(const void* table_dev, int32_t n_rows, void* dst, int32_t blocks_per_row, void* stream);
+int mdvit_table_unpack(const void* table_dev, int32_t n_rows, const void* src, int32_t blocks_per_row, void* stream);
+
 /* ---- TransFuse_S_adapt path (BASELINE configs[4]; csrc/transfuse.hip) ------------------------------------------------------------
  * What Models/Hybrid_models/TransFuseFolder/{TransFuse,vision_transformer,DeiT}.py and multi_train_TransFuse.py need beyond the MDViT
  * kernels above (dense 3x3 / 1x1 convolutions, BatchNorm, LayerNorm, Linear / MLP GEMMs and the Domain Adapter are shared).  NHWC fp32. */

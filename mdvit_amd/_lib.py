@@ -240,6 +240,9 @@ _SIGS = {
     "mdvit_factoratt_bwd": [vp] * 22 + [vp, C.c_size_t] + [i32] * 8 + [vp],
     "mdvit_seg_losses_fwd": [vp, vp, vp, vp, vp, i64, vp],
     "mdvit_adamw_step": [vp, i32, i32, vp, vp, f32, f32, f32, f32, i32, vp],
+    "mdvit_adam_step": [vp, i32, i32, vp, vp, f32, f32, f32, f32, i32, i32, vp],
+    "mdvit_table_pack": [vp, i32, vp, i32, vp],
+    "mdvit_table_unpack": [vp, i32, vp, i32, vp],
     "mdvit_seg_metrics": [vp, vp, vp, vp, vp, i64, vp],
     "mdvit_eval_accumulate": [vp, vp, vp, C.POINTER(i32), C.POINTER(i32), i32, i64, i32, vp, vp, vp, vp, C.c_size_t, vp],
     "mdvit_eval_table": [vp, i32, vp, vp],

@@ -86,6 +86,14 @@ class TrainAug:
         self.generator = torch.Generator().manual_seed(int(seed))
         self.flags: Optional[torch.Tensor] = None         # of the last batch
 
+    def state_dict(self) -> dict:
+        """the generator's state and p: the draws of the next batch are a function of these two alone"""
+        return {"p": self.p, "generator": self.generator.get_state()}
+
+    def load_state_dict(self, state_dict: dict):
+        self.p = float(state_dict["p"])
+        self.generator.set_state(state_dict["generator"])
+
     def __call__(self, img_u8: torch.Tensor, mask_u8: Optional[torch.Tensor] = None):
         from . import ops
         if img_u8.dim() != 4 or not img_u8.is_cuda:

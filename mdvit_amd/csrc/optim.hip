@@ -2,15 +2,21 @@
 // The parameters are separate tensors, their gradients views into flat buckets (parallel.GradAccumulator), the moments flat
 // buffers with the bucket layout: a device table of {param, grad, exp_avg, exp_avg_sq, numel} rows drives the kernel
 // (grid.y = table row).  Step count and learning rate live in device memory, so a captured HIP graph replays it unchanged.
+// The same kernel body serves torch.optim.Adam (coupled L2 decay, the reference's `train.optimizer.mode: 'adam'`): the decay rule is a
+// template parameter, so the AdamW instantiation holds no trace of the other rule.
 #include "common.h"
 
 namespace {
 
 struct AdamScalars { float beta1, beta2, eps, weight_decay; int zero_grad; };
 
+enum { MODE_ADAMW = 0, MODE_ADAM = 1 };
+
 // torch.optim.AdamW (amsgrad=False, maximize=False), single-tensor formulation:
 //   p *= 1 - lr*wd;  m = lerp(m, g, 1-b1);  v = b2*v + (1-b2) g^2;  p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
-__global__ __launch_bounds__(256) void adamw_kernel(const long long* __restrict__ table, const float* __restrict__ lr_dev,
+// torch.optim.Adam (MODE_ADAM): no `p *= 1 - lr*wd`; the decay enters the gradient instead, g <- g + wd*p, before the moments see it
+template <int MODE>
+__global__ __launch_bounds__(256) void adam_kernel(const long long* __restrict__ table, const float* __restrict__ lr_dev,
                                                     const float* __restrict__ step_dev, AdamScalars h) {
     const long long* row = table + 5 * (long)blockIdx.y;
     float* p = reinterpret_cast<float*>(row[0]);
@@ -31,7 +37,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(const long long* __restrict_
             float pp[4] = {pv.x, pv.y, pv.z, pv.w}, gg[4] = {gv.x, gv.y, gv.z, gv.w}, mm[4] = {mv.x, mv.y, mv.z, mv.w}, vq[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                pp[j] *= decay;
+                if constexpr (MODE == MODE_ADAMW) pp[j] *= decay;
+                else gg[j] += h.weight_decay * pp[j];
                 mm[j] = mm[j] + (gg[j] - mm[j]) * (1.0f - h.beta1);
                 vq[j] = h.beta2 * vq[j] + (1.0f - h.beta2) * gg[j] * gg[j];
                 pp[j] -= step_size * mm[j] / (sqrtf(vq[j]) * inv_sqrt_bc2 + h.eps);
@@ -43,8 +50,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(const long long* __restrict_
         }
     }
     for (long i = (vec ? nq * 4 : 0) + t0; i < n; i += stride) {
-        float pp = p[i] * decay;
-        const float gg = g[i];
+        float pp = p[i], gg = g[i];
+        if constexpr (MODE == MODE_ADAMW) pp *= decay;
+        else gg += h.weight_decay * pp;
         const float mm = m[i] + (gg - m[i]) * (1.0f - h.beta1);
         const float vq = h.beta2 * v[i] + (1.0f - h.beta2) * gg * gg;
         pp -= step_size * mm / (sqrtf(vq) * inv_sqrt_bc2 + h.eps);
@@ -57,18 +65,31 @@ __global__ void adamw_tick_kernel(float* step_dev) { if (threadIdx.x == 0 && blo
 
 }  // namespace
 
-extern "C" int mdvit_adamw_step(const void* table_dev, int32_t n_tensors, int32_t blocks_per_tensor, const float* lr_dev, float* step_dev,
-                                float beta1, float beta2, float eps, float weight_decay, int32_t zero_grad, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    MDVIT_CHECK_ARG(table_dev && lr_dev && step_dev && n_tensors > 0 && blocks_per_tensor > 0, MDVIT_E_SHAPE, "adamw_step: bad arguments");
-    MDVIT_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, MDVIT_E_SHAPE, "adamw_step: bad hyper-parameters");
+template <int MODE>
+static int adam_launch(const void* table_dev, int32_t n_tensors, int32_t blocks_per_tensor, const float* lr_dev, float* step_dev, AdamScalars h, hipStream_t s) {
     hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(64), 0, s, step_dev);
-    AdamScalars h{beta1, beta2, eps, weight_decay, zero_grad};
     // gridDim.y is limited to 65535: a table with more rows (one row per 32768-element chunk: > 2.1 G parameters) goes out in slices of the table
     for (int32_t r0 = 0; r0 < n_tensors; r0 += 65535) {
         const int32_t nr = n_tensors - r0 < 65535 ? n_tensors - r0 : 65535;
-        hipLaunchKernelGGL(adamw_kernel, dim3(blocks_per_tensor, nr), dim3(256), 0, s, (const long long*)table_dev + 5 * (long long)r0, lr_dev, (const float*)step_dev, h);
+        hipLaunchKernelGGL(adam_kernel<MODE>, dim3(blocks_per_tensor, nr), dim3(256), 0, s, (const long long*)table_dev + 5 * (long long)r0, lr_dev, (const float*)step_dev, h);
         MDVIT_LAUNCH_CHECK();
     }
     return MDVIT_OK;
+}
+
+extern "C" int mdvit_adamw_step(const void* table_dev, int32_t n_tensors, int32_t blocks_per_tensor, const float* lr_dev, float* step_dev,
+                                float beta1, float beta2, float eps, float weight_decay, int32_t zero_grad, void* stream) {
+    MDVIT_CHECK_ARG(table_dev && lr_dev && step_dev && n_tensors > 0 && blocks_per_tensor > 0, MDVIT_E_SHAPE, "adamw_step: bad arguments");
+    MDVIT_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, MDVIT_E_SHAPE, "adamw_step: bad hyper-parameters");
+    return adam_launch<MODE_ADAMW>(table_dev, n_tensors, blocks_per_tensor, lr_dev, step_dev, AdamScalars{beta1, beta2, eps, weight_decay, zero_grad}, (hipStream_t)stream);
+}
+
+extern "C" int mdvit_adam_step(const void* table_dev, int32_t n_tensors, int32_t blocks_per_tensor, const float* lr_dev, float* step_dev,
+                               float beta1, float beta2, float eps, float weight_decay, int32_t zero_grad, int32_t mode, void* stream) {
+    MDVIT_CHECK_ARG(table_dev && lr_dev && step_dev && n_tensors > 0 && blocks_per_tensor > 0, MDVIT_E_SHAPE, "adam_step: bad arguments");
+    MDVIT_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, MDVIT_E_SHAPE, "adam_step: bad hyper-parameters");
+    MDVIT_CHECK_ARG(mode == MODE_ADAMW || mode == MODE_ADAM, MDVIT_E_SHAPE, "adam_step: mode %d is neither 0 (decoupled decay, AdamW) nor 1 (coupled L2, Adam)", (int)mode);
+    const AdamScalars h{beta1, beta2, eps, weight_decay, zero_grad};
+    return mode == MODE_ADAMW ? adam_launch<MODE_ADAMW>(table_dev, n_tensors, blocks_per_tensor, lr_dev, step_dev, h, (hipStream_t)stream)
+                              : adam_launch<MODE_ADAM>(table_dev, n_tensors, blocks_per_tensor, lr_dev, step_dev, h, (hipStream_t)stream);
 }

@@ -240,6 +240,26 @@ class DomainBatches:
                 out.append((image, label, torch.full((idx.numel(),), ds.set_id, dtype=torch.int64)))
             yield out
 
+    def state_dict(self) -> dict:
+        """Where the sampling stands: every domain's generator state and the batches of its current permutation that are still queued (positions carry over
+        epoch boundaries, so both are needed), TrainAug's state, and the configuration the index stream depends on -- batch size, rank, world, the domains'
+        names and lengths -- which load_state_dict checks.  With several ranks every rank saves and loads its own: the queues are its share of the deal."""
+        return {"batch_size": self.batch_size, "rank": self.rank, "world": self.world, "lengths": {name: len(ds) for name, ds in self.datasets.items()},
+                "generators": {name: g.get_state() for name, g in self._gen.items()},
+                "queues": {name: [t.clone() for t in q] for name, q in self._queue.items()},
+                "aug": self.aug.state_dict()}
+
+    def load_state_dict(self, state_dict: dict):
+        """raises ValueError, before anything is changed, if the state was saved under another batch size, rank, world, or other domains or dataset lengths"""
+        mine = {"batch_size": self.batch_size, "rank": self.rank, "world": self.world, "lengths": {name: len(ds) for name, ds in self.datasets.items()}}
+        for key, have in mine.items():
+            if state_dict[key] != have or (key == "lengths" and list(state_dict[key]) != list(have)):
+                raise ValueError(f"DomainBatches.load_state_dict: the state was saved with {key} = {state_dict[key]}, this object has {have}")
+        for name, g in self._gen.items():
+            g.set_state(state_dict["generators"][name])
+        self._queue = {name: [torch.as_tensor(t, dtype=torch.int64).clone() for t in state_dict["queues"][name]] for name in self.datasets}
+        self.aug.load_state_dict(state_dict["aug"])
+
     def eval_loaders(self, batch_size: Optional[int] = None) -> Dict[str, Iterable]:
         """{name: sequential, unshuffled loader that keeps its short last batch} over the same datasets, for evaluate()"""
         bs = self.batch_size if batch_size is None else int(batch_size)

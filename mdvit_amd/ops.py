@@ -72,6 +72,35 @@ def _seed_ptr():
     return None if _seed_buf is None else C.c_void_p(_seed_buf.data_ptr())
 
 
+def rng_state() -> dict:
+    """What the dropout / DropPath masks of the NEXT step are a function of, for a checkpoint (snapshot.TrainState): the host counter _next_key draws from,
+    torch's initial seed (mixed into every key), the device seed words if enable_device_seed is on (a host copy: one synchronising read), and torch's
+    own generator states (the CPU fallbacks of the model code draw from them)."""
+    global _key_counter
+    n = next(_key_counter)
+    _key_counter = itertools.count(n)          # (a count cannot be read without being advanced: put the value back)
+    state = {"key_counter": int(n), "initial_seed": int(torch.initial_seed()), "device_seed": None if _seed_buf is None else _seed_buf.cpu(),
+             "torch_cpu": torch.get_rng_state()}
+    if torch.cuda.is_available():
+        state["torch_cuda"] = torch.cuda.get_rng_state()
+    return state
+
+
+def set_rng_state(state: dict):
+    """the inverse of rng_state().  The device seed words are written in place (a captured graph holds their address); a state with seed words turns the
+    device seed on if it is off, one without leaves it as it is."""
+    global _key_counter
+    torch.manual_seed(int(state["initial_seed"]))          # torch.initial_seed() has no other setter; the generator states follow
+    torch.set_rng_state(state["torch_cpu"])
+    if state.get("torch_cuda") is not None and torch.cuda.is_available():
+        torch.cuda.set_rng_state(state["torch_cuda"])
+    _key_counter = itertools.count(int(state["key_counter"]))
+    if state.get("device_seed") is not None:
+        if _seed_buf is None:
+            enable_device_seed(True)
+        _seed_buf.copy_(state["device_seed"])
+
+
 def _p(t: Optional[torch.Tensor]):
     """the tensor's device address as a plain int (None stays None): ctypes converts an int to a pointer argument / struct field itself, and building a c_void_p object
     per operand was ~0.3 us x ~4000 operands per step of pure host time"""

@@ -22,7 +22,7 @@ def main():
         keep, inside, nwin = [], False, 0
         for r in rows:
             nm = r["Kernel_Name"]
-            if "adamw_kernel" in nm:
+            if "adamw_kernel" in nm or "adam_kernel" in nm:          # (adam_kernel<MODE> since the decay rule became a template parameter)
                 inside = True; nwin += 1
                 continue
             if inside and ("seg_losses_bwd" in nm or "_bwd_kernel" in nm and "loss" in nm):
