@@ -676,6 +676,31 @@ int mdvit_eval_accumulate(const float* out, const float* aux, const float* label
  * Last row, what the reference logs (:311-313,404-408): the SUM of the per-domain losses, the MEANS of the four scores over the domains that saw images,
  * the total number of images.  A domain without images has a zero row and takes no part in the means. */
 int mdvit_eval_table(const double* acc, int32_t num_domains, float* table, void* stream);
+/* The per-image half of a test report (Utils/pieces.py:103-121 dice_per_img scores each image on its own).  out / aux / label [n][HW]: the n consecutive
+ * images of ONE forward; aux may be NULL.  With A = sigmoid(logits) > 0.5 and Y = label != 0 -- mdvit_eval_accumulate's predicates, not `logit > 0`: a tiny
+ * positive logit whose sigmoid rounds to 0.5 is background in both -- it writes
+ *   counts   [n][5] int64:  |A&Y|, |A|, |Y|, |Aaux&Y|, |Aaux| of each image (the columns of mdvit_eval_accumulate's counts; the aux columns are 0 without aux)
+ *   bits / aux_bits [n][words] uint64 (each nullable; aux_bits needs aux), words = ceil(HW / 64): bit l of word j is pixel 64 j + l of A (Aaux); the bits
+ *   past HW in the last word are 0.
+ * A word is the wave's ballot of the predicate and the counts are popcounts of the ballots: exact integers that agree with the bits by construction.
+ * Every output element is written (the caller zeroes nothing).  No atomics: per-workgroup partial rows in ws, folded in a fixed order.  ws:
+ * mdvit_eval_images_ws_bytes(n, HW) bytes (0 for n outside 1..65535 or HW outside 1..2^30: MDVIT_E_SHAPE), a short one is MDVIT_E_WORKSPACE -- both
+ * before any launch. */
+size_t mdvit_eval_images_ws_bytes(int32_t n, int64_t HW);
+int mdvit_eval_images(const float* out, const float* aux, const float* label, int32_t n, int64_t HW, int64_t* counts, uint64_t* bits, uint64_t* aux_bits,
+                      void* ws, size_t ws_bytes, void* stream);
+/* structure_loss (multi_train_TransFuse.py:29-38) image by image, forward only: the validation loss of that script (:245-259).  pred / label [n][H][W] ->
+ *   loss [n] double:     wbce_i + wiou_i = S0/S1 + 1 - (S2 + 1) / (S3 - S2 + 1); structure_loss of a batch is the MEAN of its images' terms
+ *   sums [n][4] double (nullable): S0 = sum weit bce, S1 = sum weit, S2 = sum p m weit, S3 = sum (p + m) weit (mdvit_structure_loss_fwd's sums)
+ * with mdvit_structure_weight's and mdvit_structure_loss_fwd's element expressions (products in fp32, sums in double).  The 31 x 31 zero-padded box sum
+ * (always / 961) is formed inside the kernel from a label tile with a 15-pixel halo: no [n,H,W] weight or scratch tensor, one read of pred, one haloed
+ * read of label.  For a binary label the box sums are integers <= 961, exact in fp32: weit is mdvit_structure_weight's bit for bit.  H, W any positive
+ * size up to 32768 (smaller than the window included).  No atomics: per-tile partial rows in ws, folded in a fixed order, so loss and sums are
+ * bit-reproducible (mdvit_structure_loss_fwd's double atomics are not).  ws: mdvit_eval_structure_ws_bytes(n, H, W) bytes, 8-byte aligned; error codes
+ * as mdvit_eval_images. */
+size_t mdvit_eval_structure_ws_bytes(int32_t n, int32_t H, int32_t W);
+int mdvit_eval_structure(const float* pred, const float* label, int32_t n, int32_t H, int32_t W, double* loss, double* sums, void* ws, size_t ws_bytes,
+                         void* stream);
 /* uint8 HWC image [B,H,W,3] -> fp32 CHW [B,3,H,W]:  ((float)(u8 / 255.0) - mean[c]) / std[c]  with the ImageNet mean / std
  * (create_dataset.py:25-26 norm01, :143-144,165-172 permute + transforms.Normalize), bit-exact with that sequence. */
 int mdvit_image_normalize_u8(const uint8_t* img_nhwc, float* out_nchw, int32_t B, int32_t H, int32_t W, void* stream);

@@ -3,6 +3,7 @@ nn.Module call surface.  See DESIGN.md / INTEGRATION.md."""
 from .model import BASE, BASE_DASE, BASE_DSN, BASE_USE, MDViT, MDViT_DSN  # noqa: F401
 from .losses import domain_losses, seg_loss  # noqa: F401
 from .evaluate import EvalAccumulator, evaluate  # noqa: F401
+from .report import ImageReport, unpack_masks  # noqa: F401
 from .data import DeviceDataset, DomainBatches  # noqa: F401
 from .snapshot import DeviceSnapshot, TrainState  # noqa: F401
 from .swin import SwinUnet  # noqa: F401
@@ -18,4 +19,4 @@ def load_reference_state_dict(model, state_dict, strict: bool = True):
 
 
 __all__ = ["MDViT", "MDViT_DSN", "BASE", "BASE_DSN", "BASE_DASE", "BASE_USE", "SwinUnet", "UTNet", "domain_losses", "seg_loss", "load_reference_state_dict",
-           "EvalAccumulator", "evaluate", "DeviceDataset", "DomainBatches", "DeviceSnapshot", "TrainState"]
+           "EvalAccumulator", "evaluate", "ImageReport", "unpack_masks", "DeviceDataset", "DomainBatches", "DeviceSnapshot", "TrainState"]

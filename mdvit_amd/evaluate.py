@@ -173,13 +173,17 @@ def _prepare(batch, device):
 
 
 def evaluate(model, loaders: Dict, *, num_domains: int = 4, use_domain_label: bool = True, fuse_domains: bool = True, forward: Optional[Callable] = None,
-             accumulator: Optional[EvalAccumulator] = None) -> dict:
+             accumulator: Optional[EvalAccumulator] = None, report: Optional["ImageReport"] = None) -> dict:          # noqa: F821 (report.py imports this module)
     """One validation / test epoch.  loaders: {domain name or id: iterable of (image, label, set_id)} (the contract of synthetic.make_domain_batch; a uint8
     [B,H,W,3] image goes through ops.image_normalize_u8).  The model runs in eval() under no_grad and gets its mode back.  With fuse_domains, equal-sized
     batches of different domains run as ONE domain-batched forward, model(x, label, [d0, d1, ...]) -- no operator couples samples in eval; ragged tails,
-    models whose forward takes no `d`, and a user-supplied forward(image, domain_label_or_None, d) run per domain.  Returns EvalAccumulator.result()."""
+    models whose forward takes no `d`, and a user-supplied forward(image, domain_label_or_None, d) run per domain.  Returns EvalAccumulator.result().
+    report: a report.ImageReport -- it is reset, takes every forward's logits right after the accumulator, image by image in evaluation order, and its
+    result() comes back as res["report"]; every other key is the same with and without it."""
     device = next(model.parameters()).device
     acc = (accumulator or EvalAccumulator(num_domains, device)).reset()
+    if report is not None:
+        report.reset()
     takes_d = forward is None and "d" in inspect.signature(model.forward).parameters
     fuse = bool(fuse_domains) and takes_d
 
@@ -206,7 +210,13 @@ def evaluate(model, loaders: Dict, *, num_domains: int = 4, use_domain_label: bo
                     x, label = torch.cat([p[0] for p in prepared]), torch.cat([p[1] for p in prepared])
                     d_arg = [str(d) for d in ds]
                 out, aux = split_outputs(run(x, torch.cat(set_ids) if len(step) > 1 else set_ids[0], d_arg))
-                acc.update(out, aux, label, ds, [int(p[0].shape[0]) for p in prepared])
+                images = [int(p[0].shape[0]) for p in prepared]
+                acc.update(out, aux, label, ds, images)
+                if report is not None:
+                    report.update(out, aux, label, ds, images)
     finally:
         model.train(was_training)
-    return acc.result()
+    res = acc.result()
+    if report is not None:
+        res["report"] = report.result()
+    return res

@@ -3601,6 +3601,61 @@ def eval_table(acc, table=None):
     return table
 
 
+def eval_images_ws_bytes(n: int, HW: int) -> int:
+    """bytes of eval_images' workspace for n images of HW pixels (0 for sizes the entry refuses)"""
+    return int(_lib.load().mdvit_eval_images_ws_bytes(int(n), int(HW)))
+
+
+def eval_images(out, aux, label, counts, ws, bits=None, aux_bits=None):
+    """The logits of one forward image by image, on the device and without a sync: counts [n,5] int64 receives each image's |A&Y|, |A|, |Y|, |Aaux&Y|, |Aaux|
+    (aux columns 0 with aux None); bits / aux_bits [n, ceil(HW/64)] int64 (optional) the thresholded masks, one bit per pixel (layout: mdvit_eval_images in
+    the header).  n = counts.shape[0] is the number of images, HW = out.numel() // n; ws: a device buffer of eval_images_ws_bytes(n, HW) bytes.  Every
+    element of the outputs is written."""
+    out, label = _c(out.detach()), _c(label.detach().float())
+    aux = None if aux is None else _c(aux.detach())
+    _chk(out, aux, label)
+    if not (counts.is_cuda and counts.dtype == torch.int64 and counts.dim() == 2 and counts.shape[1] == 5 and counts.is_contiguous()):
+        raise _lib.MdvitHipError("eval_images expects counts as a contiguous CUDA int64 tensor [n,5]")
+    n = counts.shape[0]
+    if n == 0 or out.numel() % n or label.numel() != out.numel() or (aux is not None and aux.numel() != out.numel()):
+        raise _lib.MdvitHipError(f"eval_images: {out.numel()} logits, {label.numel()} labels and {n} images do not fit together")
+    HW = out.numel() // n
+    words = (HW + 63) // 64
+    for name, t in (("bits", bits), ("aux_bits", aux_bits)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (n, words)):
+            raise _lib.MdvitHipError(f"eval_images expects {name} as a contiguous CUDA int64 tensor [{n},{words}]")
+    if aux is None and aux_bits is not None:
+        raise _lib.MdvitHipError("eval_images: aux_bits without aux")
+    if not ws.is_cuda or not ws.is_contiguous():
+        raise _lib.MdvitHipError("eval_images expects the workspace as a contiguous CUDA tensor")
+    call("mdvit_eval_images", _p(out), _p(aux), _p(label), n, HW, _p(counts), _p(bits), _p(aux_bits), _p(ws), ws.numel() * ws.element_size(), _stream())
+    return counts
+
+
+def eval_structure_ws_bytes(n: int, H: int, W: int) -> int:
+    """bytes of eval_structure's workspace for n images of H x W pixels (0 for sizes the entry refuses)"""
+    return int(_lib.load().mdvit_eval_structure_ws_bytes(int(n), int(H), int(W)))
+
+
+def eval_structure(pred, label, loss, ws, sums=None):
+    """structure_loss image by image (multi_train_TransFuse.py:29-38; forward only, no sync): pred / label [n,1,H,W] or [n,H,W] -> loss [n] float64, the
+    per-image term wbce + wiou whose mean over a batch is structure_loss; sums [n,4] float64 (optional) the image's S0..S3 (layout: mdvit_eval_structure in
+    the header).  ws: a device buffer of eval_structure_ws_bytes(n, H, W) bytes."""
+    pred, label = _c(pred.detach()), _c(label.detach().float())
+    _chk(pred, label)
+    if not (loss.is_cuda and loss.dtype == torch.float64 and loss.dim() == 1 and loss.is_contiguous()):
+        raise _lib.MdvitHipError("eval_structure expects loss as a contiguous CUDA float64 tensor [n]")
+    n = loss.shape[0]
+    if pred.dim() < 2 or n == 0 or pred.shape[0] != n or pred.numel() != n * pred.shape[-2] * pred.shape[-1] or label.numel() != pred.numel():
+        raise _lib.MdvitHipError(f"eval_structure expects pred and label as [n,1,H,W] or [n,H,W] with n = {n} (got {tuple(pred.shape)}, {tuple(label.shape)})")
+    if sums is not None and not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and tuple(sums.shape) == (n, 4)):
+        raise _lib.MdvitHipError(f"eval_structure expects sums as a contiguous CUDA float64 tensor [{n},4]")
+    if not ws.is_cuda or not ws.is_contiguous():
+        raise _lib.MdvitHipError("eval_structure expects the workspace as a contiguous CUDA tensor")
+    call("mdvit_eval_structure", _p(pred), _p(label), n, pred.shape[-2], pred.shape[-1], _p(loss), _p(sums), _p(ws), ws.numel() * ws.element_size(), _stream())
+    return loss
+
+
 def image_normalize_u8(img_u8_nhwc):
     """uint8 [B,H,W,3] on the device -> ImageNet-normalised fp32 [B,3,H,W] (the loader's norm01 + permute + Normalize)."""
     if img_u8_nhwc.dtype != torch.uint8 or img_u8_nhwc.dim() != 4 or img_u8_nhwc.shape[-1] != 3 or not img_u8_nhwc.is_cuda:

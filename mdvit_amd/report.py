@@ -1,0 +1,225 @@
+"""A per-image test report on the device (the reference's helper: Utils/pieces.py:103-121 dice_per_img; TransFuse's validation loss:
+multi_train_TransFuse.py:29-38,245-268): for every image of an epoch the five thresholded counts of the validation pass, optionally the per-image term of
+structure_loss and the thresholded masks packed one bit per pixel -- appended to device tables by ops.eval_images / ops.eval_structure, forward after forward,
+without a copy or a sync; result() is the epoch's single copy to the host, where Dice / IoU, their mean and std per domain and the structure-loss column are
+formed from the integer counts.
+
+    report = ImageReport(num_domains=4, masks=True, structure=True)
+    res = evaluate(model, loaders, report=report)["report"]
+    res["dice"], res["per_domain"][d]["dice_std"], res["per_domain"][d]["structure_loss"], unpack_masks(res["masks"], res["size"])
+"""
+from __future__ import annotations
+
+from typing import Dict
+
+import numpy as np
+import torch
+
+from . import ops
+from .evaluate import MAX_GROUPS
+
+_COUNT_COLUMNS = 5          # |A&Y| |A| |Y| |Aaux&Y| |Aaux| (mdvit_eval_images)
+
+
+# ------------------------------------------------------------------------------------------------
+# packed masks (host): word j of an image holds pixels 64 j .. 64 j + 63, pixel 64 j + l in bit l
+# ------------------------------------------------------------------------------------------------
+def _words(n_pixels: int) -> int:
+    return (int(n_pixels) + 63) // 64
+
+
+def pack_masks(masks) -> np.ndarray:
+    """{0, nonzero} masks [N,H,W] (numpy or torch, host) -> uint64 [N, ceil(H W / 64)], the layout ImageReport returns; the bits past H W are 0.  For tests:
+    the device packs its own."""
+    m = masks.cpu().numpy() if torch.is_tensor(masks) else np.asarray(masks)
+    n = m.shape[0]
+    flat = (m.reshape(n, -1) != 0).astype(np.uint8)
+    pad = _words(flat.shape[1]) * 64 - flat.shape[1]
+    if pad:
+        flat = np.concatenate([flat, np.zeros((n, pad), dtype=np.uint8)], axis=1)
+    return np.ascontiguousarray(np.packbits(flat, axis=1, bitorder="little")).view("<u8").astype(np.uint64, copy=False).reshape(n, -1)
+
+
+def unpack_masks(packed, size) -> np.ndarray:
+    """packed uint64 (or int64) [N, words] -> uint8 [N,H,W] in {0, 1} on the host, size = (H, W); little-endian bit order within a word"""
+    H, W = int(size[0]), int(size[1])
+    p = packed.cpu().numpy() if torch.is_tensor(packed) else np.asarray(packed)
+    if p.ndim != 2 or p.dtype.itemsize != 8 or p.shape[1] != _words(H * W):
+        raise ValueError(f"unpack_masks: expected 64-bit words [N,{_words(H * W)}] for size {(H, W)}, got {p.dtype} {p.shape}")
+    by = np.ascontiguousarray(p).view(np.uint64).astype("<u8", copy=False).view(np.uint8).reshape(p.shape[0], -1)
+    return np.unpackbits(by, axis=1, bitorder="little")[:, :H * W].reshape(p.shape[0], H, W)
+
+
+# ------------------------------------------------------------------------------------------------
+# scores from counts (host, float64)
+# ------------------------------------------------------------------------------------------------
+def _ratio(num, den):
+    """num / den with 0/0 -> 0 (mdvit_seg_metrics' rule; dice_per_img's numpy division gives NaN there)"""
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    return np.divide(num, den, out=np.zeros_like(num), where=den > 0)
+
+
+def scores_from_counts(counts, domains, structure=None) -> dict:
+    """counts int64 [N,5] and the images' domain ids [N] (+ the structure column [N]) -> the score columns of ImageReport.result(): per image
+    dice = 2|A&Y| / (|A|+|Y|), iou = |A&Y| / (|A|+|Y|-|A&Y|) for the main and auxiliary output (mdvit_seg_metrics' expressions, 0/0 -> 0) and `empty`
+    (|A|+|Y| == 0: the images where the two conventions differ); per domain that saw images the count, mean and population std of dice and iou over
+    ITS images and the mean structure term (loss_val_epoch, multi_train_TransFuse.py:259); sum_structure_loss over the domains (:268)."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1, _COUNT_COLUMNS)
+    dom = np.asarray(domains, dtype=np.int32).reshape(-1)
+    i0, a0, y, i1, a1 = (c[:, k] for k in range(_COUNT_COLUMNS))
+    res = {"domain": dom, "counts": c,
+           "dice": _ratio(2 * i0, a0 + y), "iou": _ratio(i0, a0 + y - i0), "aux_dice": _ratio(2 * i1, a1 + y), "aux_iou": _ratio(i1, a1 + y - i1),
+           "empty": (a0 + y) == 0}
+    if structure is not None:
+        res["structure"] = np.asarray(structure, dtype=np.float64).reshape(-1)
+    per: Dict[int, dict] = {}
+    for d in sorted(set(int(v) for v in dom)):
+        sel = dom == d
+        row = {"images": int(sel.sum()), "dice_mean": float(res["dice"][sel].mean()), "dice_std": float(res["dice"][sel].std()),
+               "iou_mean": float(res["iou"][sel].mean()), "iou_std": float(res["iou"][sel].std())}
+        if structure is not None:
+            row["structure_loss"] = float(res["structure"][sel].mean())
+        per[d] = row
+    res["per_domain"] = per
+    if structure is not None:
+        res["sum_structure_loss"] = float(sum(row["structure_loss"] for row in per.values()))
+    return res
+
+
+# ------------------------------------------------------------------------------------------------
+# the epoch's tables
+# ------------------------------------------------------------------------------------------------
+class ImageReport:
+    """counts [cap,5] int64, structure [cap] float64, bits / aux_bits [cap,words] int64 (uint64 words) on `device`, one row per image in update() order.
+    update() enqueues kernels and returns -- the row offset and the images' domains are host integers; result() is the one call that copies to the host.
+    The tables double when they are full (a stream-ordered device copy); `capacity` = the epoch's image count avoids that."""
+
+    def __init__(self, num_domains: int = 4, device=None, masks: bool = False, aux_masks: bool = False, structure: bool = False, capacity: int = 0):
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("ImageReport lives on a CUDA(HIP) device; there is no CPU path")
+        self.num_domains = int(num_domains)
+        self.device = device
+        self.masks, self.aux_masks, self.structure = bool(masks), bool(aux_masks), bool(structure)
+        self.capacity = max(int(capacity), 0)
+        self.size = None          # (H, W), fixed by the first update
+        self.rows = 0
+        self.domains: list = []
+        self.counts = self.structure_col = self.bits = self.aux_bits = None
+        self._cap = 0
+        self._ws = self._ws_s = None
+
+    def reset(self):
+        """forget the images (the tables, their capacity and the image size stay)"""
+        self.rows = 0
+        self.domains = []
+        return self
+
+    def _table(self, old, cap, cols, dtype):
+        t = torch.empty((cap,) + cols, device=self.device, dtype=dtype)
+        if old is not None and self.rows:
+            t[:self.rows].copy_(old[:self.rows])
+        return t
+
+    def _reserve(self, need: int):
+        if need <= self._cap:
+            return
+        cap = max(need, 2 * self._cap, self.capacity, 1)
+        words = _words(self.size[0] * self.size[1])
+        self.counts = self._table(self.counts, cap, (_COUNT_COLUMNS,), torch.int64)
+        if self.structure:
+            self.structure_col = self._table(self.structure_col, cap, (), torch.float64)
+        if self.masks:
+            self.bits = self._table(self.bits, cap, (words,), torch.int64)
+        if self.aux_masks:
+            self.aux_bits = self._table(self.aux_bits, cap, (words,), torch.int64)
+        self._cap = cap
+
+    @staticmethod
+    def _workspace(ws, nbytes):
+        return ws if ws is not None and ws.numel() * 8 >= nbytes else None
+
+    def update(self, out, aux, label, domains, images=None):
+        """logits of one forward -> one row per image.  Arguments as EvalAccumulator.update: domains an int (one domain batch) or the ids of the forward's
+        consecutive domain batches, images their sizes (default: equal parts).  Returns the number of rows the report holds."""
+        if isinstance(domains, (int, str)):
+            domains, images = [int(domains)], [out.shape[0]]
+        else:
+            domains = [int(d) for d in domains]
+            if images is None:
+                if not domains or out.shape[0] % len(domains):
+                    raise ValueError(f"batch {out.shape[0]} is not {len(domains)} equal domain batches")
+                images = [out.shape[0] // len(domains)] * len(domains)
+        images = [int(v) for v in images]
+        if len(domains) > MAX_GROUPS:
+            raise ValueError(f"at most {MAX_GROUPS} domain batches per update")
+        n = sum(images)
+        if len(images) != len(domains) or min(images) <= 0 or n != out.shape[0] or out.dim() < 3:
+            raise ValueError(f"logits {tuple(out.shape)} are not the domain batches {images} of images [..,H,W]")
+        if min(domains) < 0 or max(domains) >= self.num_domains:
+            raise ValueError(f"domains {domains}, expected 0..{self.num_domains - 1}")
+        W = int(out.shape[-1])
+        size = (out.numel() // n // W, W)          # [B,1,H,W] and [B,H,W]: (H, W); more channels stack as rows
+        if self.structure and not (out.dim() == 4 and out.shape[1] == 1):
+            raise ValueError(f"structure=True needs [B,1,H,W] logits, got {tuple(out.shape)}")
+        if self.size is None:
+            self.size = size
+        elif size != self.size:
+            raise ValueError(f"this report holds {self.size[0]} x {self.size[1]} images, got {size[0]} x {size[1]}")
+        r0, r1 = self.rows, self.rows + n
+        self._reserve(r1)
+        nbytes = ops.eval_images_ws_bytes(n, size[0] * size[1])
+        self._ws = self._workspace(self._ws, nbytes)
+        if self._ws is None:
+            self._ws = torch.empty(((nbytes + 7) // 8,), device=self.device, dtype=torch.int64)
+        aux_bits = self.aux_bits[r0:r1] if self.aux_masks else None
+        if aux is None and aux_bits is not None:
+            aux_bits.zero_()          # no auxiliary output in this forward: its masks are empty
+            aux_bits = None
+        ops.eval_images(out, aux, label, self.counts[r0:r1], self._ws, self.bits[r0:r1] if self.masks else None, aux_bits)
+        if self.structure:
+            nbytes = ops.eval_structure_ws_bytes(n, size[0], size[1])
+            self._ws_s = self._workspace(self._ws_s, nbytes)
+            if self._ws_s is None:
+                self._ws_s = torch.empty(((nbytes + 7) // 8,), device=self.device, dtype=torch.float64)
+            ops.eval_structure(out, label, self.structure_col[r0:r1], self._ws_s)
+        for d, k in zip(domains, images):
+            self.domains.extend([d] * k)
+        self.rows = r1
+        return self.rows
+
+    def result(self) -> dict:
+        """the epoch's one copy: every table into ONE pinned buffer with one copy_, then the stream is synchronised.  Host numpy arrays, one row per image
+        in update() order: "domain" int32 [N], "counts" int64 [N,5], "dice" / "iou" / "aux_dice" / "aux_iou" float64 [N] (0/0 -> 0) and "empty" bool [N]
+        (scores_from_counts), "structure" float64 [N], "masks" / "aux_masks" uint64 [N,words] (unpack_masks) when asked for, "size" (H, W), "per_domain"
+        {domain: images, dice_mean, dice_std, iou_mean, iou_std, structure_loss} and "sum_structure_loss"."""
+        N = self.rows
+        parts = []          # (name, dtype, shape)
+        if N:
+            tabs = [("counts", self.counts, np.int64)]
+            if self.structure:
+                tabs.append(("structure", self.structure_col, np.float64))
+            if self.masks:
+                tabs.append(("masks", self.bits, np.uint64))
+            if self.aux_masks:
+                tabs.append(("aux_masks", self.aux_bits, np.uint64))
+            dev = torch.cat([t[:N].reshape(-1).view(torch.uint8) for _, t, _ in tabs])          # every table is 8-byte elements: the offsets stay aligned
+            host = torch.empty((dev.numel(),), dtype=torch.uint8, pin_memory=True)
+            host.copy_(dev, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            buf, off = host.numpy(), 0
+            for name, t, dt in tabs:
+                nb = N * int(np.prod(t.shape[1:], dtype=np.int64)) * 8
+                parts.append((name, buf[off:off + nb].view(dt).reshape((N,) + tuple(t.shape[1:])).copy()))
+                off += nb
+        got = dict(parts)
+        res = scores_from_counts(got.get("counts", np.zeros((0, _COUNT_COLUMNS), dtype=np.int64)), np.asarray(self.domains, dtype=np.int32),
+                                 got.get("structure", np.zeros((0,), dtype=np.float64)) if self.structure else None)
+        words = _words(self.size[0] * self.size[1]) if self.size else 0
+        for name, on in (("masks", self.masks), ("aux_masks", self.aux_masks)):
+            if on:
+                res[name] = got.get(name, np.zeros((0, words), dtype=np.uint64))
+        res["size"] = self.size
+        return res
