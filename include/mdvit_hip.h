@@ -701,6 +701,22 @@ int mdvit_eval_images(const float* out, const float* aux, const float* label, in
 size_t mdvit_eval_structure_ws_bytes(int32_t n, int32_t H, int32_t W);
 int mdvit_eval_structure(const float* pred, const float* label, int32_t n, int32_t H, int32_t W, double* loss, double* sums, void* ws, size_t ws_bytes,
                          void* stream);
+/* Boundary distances of the per-image report: medpy 0.4.0 metric/binary.py __surface_distances (voxelspacing None, connectivity 1) on one 2-D image at a
+ * time, for hd95 / hd / assd / asd.  out / aux / label [n][H][W]: the n consecutive images of ONE forward; aux may be NULL.  A = sigmoid(logits) > 0.5 and
+ * Y = label != 0 are mdvit_eval_images' predicates.  border(M): the set pixels of M whose four 4-neighbours are not all inside the image and set (M ^
+ * binary_erosion(M), border_value 0).  d^2 over A -> Y: for every border pixel of A the squared Euclidean distance to the nearest border pixel of Y, an
+ * integer.  Index o = 0 is the main output against the label, o = 1 the auxiliary output against the label.
+ *   rows [n][2][6] int64:  nA = |border(A)|, nY = |border(Y)|, max d^2 over A -> Y, max d^2 over Y -> A, and the order statistics of the nA + nY stacked
+ *                          d^2 at the 0-based ascending ranks floor(h) and ceil(h), h = 0.95 * (nA + nY - 1) in fp64 (numpy.percentile(., 95), linear)
+ *   sums [n][2][2] double: sum of sqrt((double)d^2) over A -> Y, then over Y -> A, each added in a fixed order
+ * With nA == 0 or nY == 0 the other four integers and both sums are 0 (medpy raises there; the host marks the image invalid); with aux NULL the o = 1 rows
+ * and sums are zeros.  Every element of both outputs is written on every call, and a call is bit-reproducible: integer LDS atomics only, no floating-point
+ * atomics.  MDVIT_E_SHAPE for a NULL out / label / rows / sums, n outside 1..65535 or H or W outside 1..1024 (d^2 <= 2 * 1023^2 < 2^21);
+ * mdvit_eval_boundary_ws_bytes returns 0 for the same sizes.  ws: that many bytes, 8-byte aligned like rows and sums (MDVIT_E_ALIGN); a short one is
+ * MDVIT_E_WORKSPACE.  All refusals come before any launch. */
+size_t mdvit_eval_boundary_ws_bytes(int32_t n, int32_t H, int32_t W);
+int mdvit_eval_boundary(const float* out, const float* aux, const float* label, int32_t n, int32_t H, int32_t W, int64_t* rows, double* sums, void* ws,
+                        size_t ws_bytes, void* stream);
 /* uint8 HWC image [B,H,W,3] -> fp32 CHW [B,3,H,W]:  ((float)(u8 / 255.0) - mean[c]) / std[c]  with the ImageNet mean / std
  * (create_dataset.py:25-26 norm01, :143-144,165-172 permute + transforms.Normalize), bit-exact with that sequence. */
 int mdvit_image_normalize_u8(const uint8_t* img_nhwc, float* out_nchw, int32_t B, int32_t H, int32_t W, void* stream);

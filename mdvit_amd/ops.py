@@ -3656,6 +3656,34 @@ def eval_structure(pred, label, loss, ws, sums=None):
     return loss
 
 
+def eval_boundary_ws_bytes(n: int, H: int, W: int) -> int:
+    """bytes of eval_boundary's workspace for n images of H x W pixels (0 for sizes the entry refuses)"""
+    return int(_lib.load().mdvit_eval_boundary_ws_bytes(int(n), int(H), int(W)))
+
+
+def eval_boundary(out, aux, label, rows, sums, ws):
+    """The boundary distances of one forward image by image (medpy's __surface_distances; forward only, no sync): out / aux / label [n,1,H,W] or [n,H,W]
+    (aux may be None) -> rows [n,2,6] int64 and sums [n,2,2] float64 (layout: mdvit_eval_boundary in the header), index 0 of the middle axis the main
+    output against the label, index 1 the auxiliary output (zeros with aux None).  H, W <= 1024.  ws: a device buffer of eval_boundary_ws_bytes(n, H, W)
+    bytes.  Every element of the outputs is written; report.boundary_from_rows forms hd95 / hd / assd from them on the host."""
+    out, label = _c(out.detach()), _c(label.detach().float())
+    aux = None if aux is None else _c(aux.detach())
+    _chk(out, aux, label)
+    if not (rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 3 and tuple(rows.shape[1:]) == (2, 6) and rows.is_contiguous()):
+        raise _lib.MdvitHipError("eval_boundary expects rows as a contiguous CUDA int64 tensor [n,2,6]")
+    n = rows.shape[0]
+    if not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and tuple(sums.shape) == (n, 2, 2)):
+        raise _lib.MdvitHipError(f"eval_boundary expects sums as a contiguous CUDA float64 tensor [{n},2,2]")
+    if out.dim() < 2 or n == 0 or out.shape[0] != n or out.numel() != n * out.shape[-2] * out.shape[-1] or label.numel() != out.numel() \
+            or (aux is not None and aux.numel() != out.numel()):
+        raise _lib.MdvitHipError(f"eval_boundary expects out, aux and label as [n,1,H,W] or [n,H,W] with n = {n} (got {tuple(out.shape)}, {tuple(label.shape)})")
+    if not ws.is_cuda or not ws.is_contiguous():
+        raise _lib.MdvitHipError("eval_boundary expects the workspace as a contiguous CUDA tensor")
+    call("mdvit_eval_boundary", _p(out), _p(aux), _p(label), n, out.shape[-2], out.shape[-1], _p(rows), _p(sums), _p(ws), ws.numel() * ws.element_size(),
+         _stream())
+    return rows
+
+
 def image_normalize_u8(img_u8_nhwc):
     """uint8 [B,H,W,3] on the device -> ImageNet-normalised fp32 [B,3,H,W] (the loader's norm01 + permute + Normalize)."""
     if img_u8_nhwc.dtype != torch.uint8 or img_u8_nhwc.dim() != 4 or img_u8_nhwc.shape[-1] != 3 or not img_u8_nhwc.is_cuda:

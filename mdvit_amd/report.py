@@ -2,7 +2,8 @@
 multi_train_TransFuse.py:29-38,245-268): for every image of an epoch the five thresholded counts of the validation pass, optionally the per-image term of
 structure_loss and the thresholded masks packed one bit per pixel -- appended to device tables by ops.eval_images / ops.eval_structure, forward after forward,
 without a copy or a sync; result() is the epoch's single copy to the host, where Dice / IoU, their mean and std per domain and the structure-loss column are
-formed from the integer counts.
+formed from the integer counts.  boundary=True adds the boundary distances medpy.metric.binary scores with (hd95, hd, assd, asd; ops.eval_boundary): two more
+tables in the same copy, the scores formed on the host by boundary_from_rows.
 
     report = ImageReport(num_domains=4, masks=True, structure=True)
     res = evaluate(model, loaders, report=report)["report"]
@@ -19,6 +20,8 @@ from . import ops
 from .evaluate import MAX_GROUPS
 
 _COUNT_COLUMNS = 5          # |A&Y| |A| |Y| |Aaux&Y| |Aaux| (mdvit_eval_images)
+_BOUNDARY_COLUMNS = 6       # nA nY max d2(A->Y) max d2(Y->A) d2 at rank floor(h), ceil(h) (mdvit_eval_boundary), per output
+_BOUNDARY_MAX_SIDE = 1024   # mdvit_eval_boundary's limit on H and W
 
 
 # ------------------------------------------------------------------------------------------------
@@ -87,14 +90,56 @@ def scores_from_counts(counts, domains, structure=None) -> dict:
 
 
 # ------------------------------------------------------------------------------------------------
+# boundary scores from rows (host, float64)
+# ------------------------------------------------------------------------------------------------
+def boundary_from_rows(rows, sums, domains) -> dict:
+    """rows int64 [N,2,6], sums float64 [N,2,2] (mdvit_eval_boundary's tables) and the images' domain ids [N] -> the boundary columns of
+    ImageReport.result(), medpy.metric.binary's hd95 / hd / assd / asd (voxelspacing None, connectivity 1) per image:
+        hd95 = sqrt(lo) + (h - floor(h)) (sqrt(hi) - sqrt(lo)),  h = 0.95 (nA + nY - 1)      numpy.percentile(., 95) of the stacked distances
+        hd = sqrt(max d2),  asd_pred_to_label = S(A->Y) / nA,  asd_label_to_pred = S(Y->A) / nY,  assd = their mean
+    and boundary_valid = nA > 0 and nY > 0; the same six with the prefix aux_ for the auxiliary output.  medpy raises for an empty mask: here the image is
+    invalid, its scores are NaN, and the statistics leave it out.  "per_domain" {domain: hd95_mean, hd95_std (population), assd_mean, assd_std,
+    boundary_images} over the domain's valid images of the main output (NaN and 0 when it has none)."""
+    r = np.asarray(rows, dtype=np.int64).reshape(-1, 2, _BOUNDARY_COLUMNS)
+    s = np.asarray(sums, dtype=np.float64).reshape(-1, 2, 2)
+    dom = np.asarray(domains, dtype=np.int32).reshape(-1)
+    res = {}
+    for o, pre in ((0, ""), (1, "aux_")):
+        na, ny = r[:, o, 0], r[:, o, 1]
+        valid = (na > 0) & (ny > 0)
+        h = 0.95 * (na + ny - 1).astype(np.float64)
+        lo, hi = np.sqrt(r[:, o, 4].astype(np.float64)), np.sqrt(r[:, o, 5].astype(np.float64))
+        nan = np.full(len(r), np.nan)
+        den_a, den_y = np.maximum(na, 1).astype(np.float64), np.maximum(ny, 1).astype(np.float64)
+        a2y, y2a = s[:, o, 0] / den_a, s[:, o, 1] / den_y
+        res[pre + "hd95"] = np.where(valid, lo + (h - np.floor(h)) * (hi - lo), nan)
+        res[pre + "hd"] = np.where(valid, np.sqrt(np.maximum(r[:, o, 2], r[:, o, 3]).astype(np.float64)), nan)
+        res[pre + "assd"] = np.where(valid, (a2y + y2a) / 2.0, nan)
+        res[pre + "asd_pred_to_label"] = np.where(valid, a2y, nan)
+        res[pre + "asd_label_to_pred"] = np.where(valid, y2a, nan)
+        res[pre + "boundary_valid"] = valid
+    per: Dict[int, dict] = {}
+    for d in sorted(set(int(v) for v in dom)):
+        sel = (dom == d) & res["boundary_valid"]
+        k = int(sel.sum())
+        stat = lambda col, fn: float(fn(res[col][sel])) if k else float("nan")
+        per[d] = {"hd95_mean": stat("hd95", np.mean), "hd95_std": stat("hd95", np.std), "assd_mean": stat("assd", np.mean), "assd_std": stat("assd", np.std),
+                  "boundary_images": k}
+    res["per_domain"] = per
+    return res
+
+
+# ------------------------------------------------------------------------------------------------
 # the epoch's tables
 # ------------------------------------------------------------------------------------------------
 class ImageReport:
-    """counts [cap,5] int64, structure [cap] float64, bits / aux_bits [cap,words] int64 (uint64 words) on `device`, one row per image in update() order.
+    """counts [cap,5] int64, structure [cap] float64, bits / aux_bits [cap,words] int64 (uint64 words), boundary_rows [cap,2,6] int64 and boundary_sums
+    [cap,2,2] float64 on `device`, one row per image in update() order.
     update() enqueues kernels and returns -- the row offset and the images' domains are host integers; result() is the one call that copies to the host.
     The tables double when they are full (a stream-ordered device copy); `capacity` = the epoch's image count avoids that."""
 
-    def __init__(self, num_domains: int = 4, device=None, masks: bool = False, aux_masks: bool = False, structure: bool = False, capacity: int = 0):
+    def __init__(self, num_domains: int = 4, device=None, masks: bool = False, aux_masks: bool = False, structure: bool = False, capacity: int = 0,
+                 boundary: bool = False):
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         device = torch.device(device)
@@ -103,13 +148,14 @@ class ImageReport:
         self.num_domains = int(num_domains)
         self.device = device
         self.masks, self.aux_masks, self.structure = bool(masks), bool(aux_masks), bool(structure)
+        self.boundary = bool(boundary)
         self.capacity = max(int(capacity), 0)
         self.size = None          # (H, W), fixed by the first update
         self.rows = 0
         self.domains: list = []
-        self.counts = self.structure_col = self.bits = self.aux_bits = None
+        self.counts = self.structure_col = self.bits = self.aux_bits = self.boundary_rows = self.boundary_sums = None
         self._cap = 0
-        self._ws = self._ws_s = None
+        self._ws = self._ws_s = self._ws_b = None
 
     def reset(self):
         """forget the images (the tables, their capacity and the image size stay)"""
@@ -135,6 +181,9 @@ class ImageReport:
             self.bits = self._table(self.bits, cap, (words,), torch.int64)
         if self.aux_masks:
             self.aux_bits = self._table(self.aux_bits, cap, (words,), torch.int64)
+        if self.boundary:
+            self.boundary_rows = self._table(self.boundary_rows, cap, (2, _BOUNDARY_COLUMNS), torch.int64)
+            self.boundary_sums = self._table(self.boundary_sums, cap, (2, 2), torch.float64)
         self._cap = cap
 
     @staticmethod
@@ -164,6 +213,11 @@ class ImageReport:
         size = (out.numel() // n // W, W)          # [B,1,H,W] and [B,H,W]: (H, W); more channels stack as rows
         if self.structure and not (out.dim() == 4 and out.shape[1] == 1):
             raise ValueError(f"structure=True needs [B,1,H,W] logits, got {tuple(out.shape)}")
+        if self.boundary:
+            if not ((out.dim() == 4 and out.shape[1] == 1) or out.dim() == 3):
+                raise ValueError(f"boundary=True needs [B,1,H,W] or [B,H,W] logits, got {tuple(out.shape)}")
+            if max(size) > _BOUNDARY_MAX_SIDE:
+                raise ValueError(f"boundary=True takes images up to {_BOUNDARY_MAX_SIDE} x {_BOUNDARY_MAX_SIDE}, got {size[0]} x {size[1]}")
         if self.size is None:
             self.size = size
         elif size != self.size:
@@ -185,6 +239,12 @@ class ImageReport:
             if self._ws_s is None:
                 self._ws_s = torch.empty(((nbytes + 7) // 8,), device=self.device, dtype=torch.float64)
             ops.eval_structure(out, label, self.structure_col[r0:r1], self._ws_s)
+        if self.boundary:
+            nbytes = ops.eval_boundary_ws_bytes(n, size[0], size[1])
+            self._ws_b = self._workspace(self._ws_b, nbytes)
+            if self._ws_b is None:
+                self._ws_b = torch.empty(((nbytes + 7) // 8,), device=self.device, dtype=torch.int64)
+            ops.eval_boundary(out, aux, label, self.boundary_rows[r0:r1], self.boundary_sums[r0:r1], self._ws_b)
         for d, k in zip(domains, images):
             self.domains.extend([d] * k)
         self.rows = r1
@@ -194,7 +254,9 @@ class ImageReport:
         """the epoch's one copy: every table into ONE pinned buffer with one copy_, then the stream is synchronised.  Host numpy arrays, one row per image
         in update() order: "domain" int32 [N], "counts" int64 [N,5], "dice" / "iou" / "aux_dice" / "aux_iou" float64 [N] (0/0 -> 0) and "empty" bool [N]
         (scores_from_counts), "structure" float64 [N], "masks" / "aux_masks" uint64 [N,words] (unpack_masks) when asked for, "size" (H, W), "per_domain"
-        {domain: images, dice_mean, dice_std, iou_mean, iou_std, structure_loss} and "sum_structure_loss"."""
+        {domain: images, dice_mean, dice_std, iou_mean, iou_std, structure_loss} and "sum_structure_loss".  With boundary=True also boundary_from_rows'
+        columns ("hd95", "hd", "assd", "asd_pred_to_label", "asd_label_to_pred", "boundary_valid" and their aux_ twins; NaN where a mask is empty), its
+        per-domain keys inside "per_domain" and "boundary_rows", the raw int64 table [N,2,6]."""
         N = self.rows
         parts = []          # (name, dtype, shape)
         if N:
@@ -205,6 +267,9 @@ class ImageReport:
                 tabs.append(("masks", self.bits, np.uint64))
             if self.aux_masks:
                 tabs.append(("aux_masks", self.aux_bits, np.uint64))
+            if self.boundary:
+                tabs.append(("boundary_rows", self.boundary_rows, np.int64))
+                tabs.append(("boundary_sums", self.boundary_sums, np.float64))
             dev = torch.cat([t[:N].reshape(-1).view(torch.uint8) for _, t, _ in tabs])          # every table is 8-byte elements: the offsets stay aligned
             host = torch.empty((dev.numel(),), dtype=torch.uint8, pin_memory=True)
             host.copy_(dev, non_blocking=True)
@@ -222,4 +287,11 @@ class ImageReport:
             if on:
                 res[name] = got.get(name, np.zeros((0, words), dtype=np.uint64))
         res["size"] = self.size
+        if self.boundary:
+            rows = got.get("boundary_rows", np.zeros((0, 2, _BOUNDARY_COLUMNS), dtype=np.int64))
+            b = boundary_from_rows(rows, got.get("boundary_sums", np.zeros((0, 2, 2), dtype=np.float64)), res["domain"])
+            for d, row in b.pop("per_domain").items():
+                res["per_domain"][d].update(row)
+            res.update(b)
+            res["boundary_rows"] = rows
         return res
