@@ -717,6 +717,29 @@ int mdvit_eval_structure(const float* pred, const float* label, int32_t n, int32
 size_t mdvit_eval_boundary_ws_bytes(int32_t n, int32_t H, int32_t W);
 int mdvit_eval_boundary(const float* out, const float* aux, const float* label, int32_t n, int32_t H, int32_t W, int64_t* rows, double* sums, void* ws,
                         size_t ws_bytes, void* stream);
+/* Connected-component post-processing of the per-image report: scipy.ndimage.label / binary_fill_holes with the default structure (connectivity 1, the four
+ * neighbours; the connectivity of mdvit_eval_boundary) on one 2-D image at a time.  out / aux / label [n][H][W]: the n consecutive images of ONE forward;
+ * aux may be NULL.  A = sigmoid(logits) > 0.5 and Y = label != 0 are mdvit_eval_images' predicates.  For a mask M: the ROOT LABEL of a component is 1 + the
+ * flat row-major index of its first pixel in raster order (renumbered by rank: ndimage.label's numbers); fill(M) = M | every 4-connected component of the
+ * background INSIDE the image that touches none of the four edges (binary_fill_holes); largest(M) = the component with the most pixels, ties to the smallest
+ * root label, an empty mask stays empty.  mode: 1 "fill" A' = fill(A), 2 "largest" A' = largest(A), 3 "fill_largest" A' = largest(fill(A)).
+ *   counts [n][5] int64:    mdvit_eval_images' columns on the cleaned masks: |A'&Y|, |A'|, |Y|, |Aaux'&Y|, |Aaux'|
+ *   rows   [n][3][4] int64: per set (0 A, 1 Aaux, 2 Y): components and largest area of the RAW mask (0 when empty), pixels the fill step set (0 in mode 2),
+ *                           pixels the largest step cleared (0 in mode 1).  The label is counted, never cleaned: its last two are 0.  With aux NULL set 1 is zeros.
+ *   bits / aux_bits [n][words] uint64 (each nullable; aux_bits needs aux): the cleaned masks in mdvit_eval_images' layout, words = ceil(H W / 64)
+ * Every element of every output is written on every call, and a call is bit-reproducible: the only atomics are 32-bit integer atomicMin / atomicAdd /
+ * atomicOr, whose results do not depend on the order; no workgroup waits on another.  MDVIT_E_SHAPE for a NULL out / label / counts / rows, n outside
+ * 1..65535, H or W outside 1..1024, a mode outside 1..3 or aux_bits without aux; mdvit_eval_components_ws_bytes returns 0 for the same sizes.  ws: that many
+ * bytes, 8-byte aligned like counts / rows / bits / aux_bits (MDVIT_E_ALIGN); a short one is MDVIT_E_WORKSPACE.  All refusals come before any launch. */
+size_t mdvit_eval_components_ws_bytes(int32_t n, int32_t H, int32_t W);
+int mdvit_eval_components(const float* out, const float* aux, const float* label, int32_t n, int32_t H, int32_t W, int32_t mode, int64_t* counts,
+                          int64_t* rows, uint64_t* bits, uint64_t* aux_bits, void* ws, size_t ws_bytes, void* stream);
+/* The labelling alone.  masks [n][H][W] uint8, nonzero = set -> labels [n][H][W] int32: the root label of every set pixel (above), 0 for background;
+ * components [n] int64 (nullable): the number of components of each image.  Sizes, workspace (mdvit_label_components_ws_bytes, 8-byte aligned like
+ * components) and error codes as mdvit_eval_components; MDVIT_E_SHAPE for a NULL masks / labels. */
+size_t mdvit_label_components_ws_bytes(int32_t n, int32_t H, int32_t W);
+int mdvit_label_components(const uint8_t* masks, int32_t n, int32_t H, int32_t W, int32_t* labels, int64_t* components, void* ws, size_t ws_bytes,
+                           void* stream);
 /* uint8 HWC image [B,H,W,3] -> fp32 CHW [B,3,H,W]:  ((float)(u8 / 255.0) - mean[c]) / std[c]  with the ImageNet mean / std
  * (create_dataset.py:25-26 norm01, :143-144,165-172 permute + transforms.Normalize), bit-exact with that sequence. */
 int mdvit_image_normalize_u8(const uint8_t* img_nhwc, float* out_nchw, int32_t B, int32_t H, int32_t W, void* stream);

@@ -249,6 +249,8 @@ _SIGS = {
     "mdvit_eval_images": [vp, vp, vp, i32, i64, vp, vp, vp, vp, C.c_size_t, vp],
     "mdvit_eval_structure": [vp, vp, i32, i32, i32, vp, vp, vp, C.c_size_t, vp],
     "mdvit_eval_boundary": [vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_size_t, vp],
+    "mdvit_eval_components": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, vp],
+    "mdvit_label_components": [vp, i32, i32, i32, vp, vp, vp, C.c_size_t, vp],
     "mdvit_image_normalize_u8": [vp, vp, i32, i32, i32, vp],
     "mdvit_augment_normalize_u8": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "mdvit_augment_probe_taps": [f32, f32, i32, i32, C.POINTER(i32), C.POINTER(f32)],
@@ -368,6 +370,10 @@ def _attach_prototypes(lib):
     lib.mdvit_eval_structure_ws_bytes.argtypes = [i32, i32, i32]
     lib.mdvit_eval_boundary_ws_bytes.restype = C.c_size_t
     lib.mdvit_eval_boundary_ws_bytes.argtypes = [i32, i32, i32]
+    lib.mdvit_eval_components_ws_bytes.restype = C.c_size_t
+    lib.mdvit_eval_components_ws_bytes.argtypes = [i32, i32, i32]
+    lib.mdvit_label_components_ws_bytes.restype = C.c_size_t
+    lib.mdvit_label_components_ws_bytes.argtypes = [i32, i32, i32]
     lib.mdvit_winattn_bwd_ws_bytes.restype = C.c_size_t
     lib.mdvit_winattn_bwd_ws_bytes.argtypes = [i32, i32, i32, i32]
     lib.mdvit_lrattn_bwd_ws_bytes.restype = C.c_size_t

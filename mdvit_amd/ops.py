@@ -3684,6 +3684,69 @@ def eval_boundary(out, aux, label, rows, sums, ws):
     return rows
 
 
+def eval_components_ws_bytes(n: int, H: int, W: int) -> int:
+    """bytes of eval_components' workspace for n images of H x W pixels (0 for sizes the entry refuses)"""
+    return int(_lib.load().mdvit_eval_components_ws_bytes(int(n), int(H), int(W)))
+
+
+def eval_components(out, aux, label, mode, counts, rows, ws, bits=None, aux_bits=None):
+    """Connected-component clean-up of one forward image by image (scipy.ndimage.label / binary_fill_holes, connectivity 1; forward only, no sync): out / aux /
+    label [n,1,H,W] or [n,H,W] (aux may be None), mode 1 "fill", 2 "largest", 3 "fill_largest" (report.postprocess_mode) -> counts [n,5] int64 (eval_images'
+    columns on the cleaned masks), rows [n,3,4] int64 (per set: components, largest area, filled, removed) and optionally bits / aux_bits [n, ceil(HW/64)]
+    int64, the cleaned masks one bit per pixel (layout: mdvit_eval_components in the header).  H, W <= 1024.  ws: a device buffer of
+    eval_components_ws_bytes(n, H, W) bytes.  Every element of the outputs is written."""
+    out, label = _c(out.detach()), _c(label.detach().float())
+    aux = None if aux is None else _c(aux.detach())
+    _chk(out, aux, label)
+    if not (counts.is_cuda and counts.dtype == torch.int64 and counts.dim() == 2 and counts.shape[1] == 5 and counts.is_contiguous()):
+        raise _lib.MdvitHipError("eval_components expects counts as a contiguous CUDA int64 tensor [n,5]")
+    n = counts.shape[0]
+    if not (rows.is_cuda and rows.dtype == torch.int64 and rows.is_contiguous() and tuple(rows.shape) == (n, 3, 4)):
+        raise _lib.MdvitHipError(f"eval_components expects rows as a contiguous CUDA int64 tensor [{n},3,4]")
+    if out.dim() < 2 or n == 0 or out.shape[0] != n or out.numel() != n * out.shape[-2] * out.shape[-1] or label.numel() != out.numel() \
+            or (aux is not None and aux.numel() != out.numel()):
+        raise _lib.MdvitHipError(f"eval_components expects out, aux and label as [n,1,H,W] or [n,H,W] with n = {n} (got {tuple(out.shape)}, {tuple(label.shape)})")
+    words = (out.shape[-2] * out.shape[-1] + 63) // 64
+    for name, t in (("bits", bits), ("aux_bits", aux_bits)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (n, words)):
+            raise _lib.MdvitHipError(f"eval_components expects {name} as a contiguous CUDA int64 tensor [{n},{words}]")
+    if aux is None and aux_bits is not None:
+        raise _lib.MdvitHipError("eval_components: aux_bits without aux")
+    if not ws.is_cuda or not ws.is_contiguous():
+        raise _lib.MdvitHipError("eval_components expects the workspace as a contiguous CUDA tensor")
+    call("mdvit_eval_components", _p(out), _p(aux), _p(label), n, out.shape[-2], out.shape[-1], int(mode), _p(counts), _p(rows), _p(bits), _p(aux_bits),
+         _p(ws), ws.numel() * ws.element_size(), _stream())
+    return counts
+
+
+def label_components_ws_bytes(n: int, H: int, W: int) -> int:
+    """bytes of label_components' workspace for n images of H x W pixels (0 for sizes the entry refuses)"""
+    return int(_lib.load().mdvit_label_components_ws_bytes(int(n), int(H), int(W)))
+
+
+def label_components(masks, components=None, ws=None):
+    """4-connected component labelling on the device (no sync): masks [n,H,W] (bool or any dtype, nonzero = set) -> int32 [n,H,W], the root label of every set
+    pixel (1 + the flat index of the first pixel of its component in raster order; renumbered by rank these are scipy.ndimage.label's numbers), 0 for
+    background.  components: an optional int64 [n] that receives the component counts.  H, W <= 1024.  ws: an optional device buffer of
+    label_components_ws_bytes(n, H, W) bytes (allocated when None)."""
+    if not masks.is_cuda or masks.dim() != 3 or masks.shape[0] == 0:
+        raise _lib.MdvitHipError(f"label_components expects a CUDA tensor [n,H,W], got {masks.device.type} {tuple(masks.shape)}")
+    m = _c((masks.detach() != 0).view(torch.uint8) if masks.dtype != torch.uint8 else masks.detach())
+    n, H, W = m.shape
+    if components is not None and not (components.is_cuda and components.dtype == torch.int64 and components.is_contiguous() and tuple(components.shape) == (n,)):
+        raise _lib.MdvitHipError(f"label_components expects components as a contiguous CUDA int64 tensor [{n}]")
+    nbytes = label_components_ws_bytes(n, H, W)
+    if nbytes == 0:
+        raise _lib.MdvitHipError(f"label_components takes 1..65535 images of up to 1024 x 1024, got {n} of {H} x {W}")
+    if ws is None:
+        ws = torch.empty(((nbytes + 7) // 8,), device=m.device, dtype=torch.int64)
+    elif not ws.is_cuda or not ws.is_contiguous():
+        raise _lib.MdvitHipError("label_components expects the workspace as a contiguous CUDA tensor")
+    labels = torch.empty((n, H, W), device=m.device, dtype=torch.int32)
+    call("mdvit_label_components", _p(m), n, H, W, _p(labels), _p(components), _p(ws), ws.numel() * ws.element_size(), _stream())
+    return labels
+
+
 def image_normalize_u8(img_u8_nhwc):
     """uint8 [B,H,W,3] on the device -> ImageNet-normalised fp32 [B,3,H,W] (the loader's norm01 + permute + Normalize)."""
     if img_u8_nhwc.dtype != torch.uint8 or img_u8_nhwc.dim() != 4 or img_u8_nhwc.shape[-1] != 3 or not img_u8_nhwc.is_cuda:

@@ -3,7 +3,8 @@ multi_train_TransFuse.py:29-38,245-268): for every image of an epoch the five th
 structure_loss and the thresholded masks packed one bit per pixel -- appended to device tables by ops.eval_images / ops.eval_structure, forward after forward,
 without a copy or a sync; result() is the epoch's single copy to the host, where Dice / IoU, their mean and std per domain and the structure-loss column are
 formed from the integer counts.  boundary=True adds the boundary distances medpy.metric.binary scores with (hd95, hd, assd, asd; ops.eval_boundary): two more
-tables in the same copy, the scores formed on the host by boundary_from_rows.
+tables in the same copy, the scores formed on the host by boundary_from_rows.  postprocess="fill" | "largest" | "fill_largest" adds the connected-component
+clean-up of the thresholded masks (scipy.ndimage's binary_fill_holes / label, connectivity 1; ops.eval_components) and the scores of the cleaned masks.
 
     report = ImageReport(num_domains=4, masks=True, structure=True)
     res = evaluate(model, loaders, report=report)["report"]
@@ -22,6 +23,9 @@ from .evaluate import MAX_GROUPS
 _COUNT_COLUMNS = 5          # |A&Y| |A| |Y| |Aaux&Y| |Aaux| (mdvit_eval_images)
 _BOUNDARY_COLUMNS = 6       # nA nY max d2(A->Y) max d2(Y->A) d2 at rank floor(h), ceil(h) (mdvit_eval_boundary), per output
 _BOUNDARY_MAX_SIDE = 1024   # mdvit_eval_boundary's limit on H and W
+_PP_MODES = {"fill": 1, "largest": 2, "fill_largest": 3}          # mdvit_eval_components' mode argument
+_PP_ROW = (3, 4)            # per set (main, auxiliary, label): components, largest area, filled, removed (mdvit_eval_components)
+_PP_MAX_SIDE = 1024         # mdvit_eval_components' limit on H and W
 
 
 # ------------------------------------------------------------------------------------------------
@@ -130,16 +134,40 @@ def boundary_from_rows(rows, sums, domains) -> dict:
 
 
 # ------------------------------------------------------------------------------------------------
+# connected-component post-processing (host side)
+# ------------------------------------------------------------------------------------------------
+def postprocess_mode(name) -> int:
+    """"fill" | "largest" | "fill_largest" -> mdvit_eval_components' mode (1, 2, 3); anything else is a ValueError (connectivity is always 1)"""
+    if not isinstance(name, str) or name not in _PP_MODES:
+        raise ValueError(f"postprocess must be None or one of {sorted(_PP_MODES)}, got {name!r}")
+    return _PP_MODES[name]
+
+
+def postprocess_from_rows(pp_counts, pp_rows, domains) -> dict:
+    """pp_counts int64 [N,5] (eval_images' columns on the cleaned masks), pp_rows int64 [N,3,4] (mdvit_eval_components' rows) and the images' domain ids [N]
+    -> the post-processing columns of ImageReport.result(): "pp_counts", "pp_dice" / "pp_iou" / "pp_aux_dice" / "pp_aux_iou" (scores_from_counts'
+    expressions, 0/0 -> 0), "components" / "largest_area" (of the RAW masks) / "filled" / "removed" int64 [N,3] (main, auxiliary, label), and "per_domain"
+    {domain: pp_dice_mean, pp_dice_std (population), pp_iou_mean, pp_iou_std}."""
+    sc = scores_from_counts(pp_counts, domains)
+    r = np.asarray(pp_rows, dtype=np.int64).reshape((-1,) + _PP_ROW)
+    res = {"pp_counts": sc["counts"], "pp_dice": sc["dice"], "pp_iou": sc["iou"], "pp_aux_dice": sc["aux_dice"], "pp_aux_iou": sc["aux_iou"],
+           "components": r[:, :, 0].copy(), "largest_area": r[:, :, 1].copy(), "filled": r[:, :, 2].copy(), "removed": r[:, :, 3].copy()}
+    res["per_domain"] = {d: {"pp_" + k: row[k] for k in ("dice_mean", "dice_std", "iou_mean", "iou_std")} for d, row in sc["per_domain"].items()}
+    return res
+
+
+# ------------------------------------------------------------------------------------------------
 # the epoch's tables
 # ------------------------------------------------------------------------------------------------
 class ImageReport:
     """counts [cap,5] int64, structure [cap] float64, bits / aux_bits [cap,words] int64 (uint64 words), boundary_rows [cap,2,6] int64 and boundary_sums
-    [cap,2,2] float64 on `device`, one row per image in update() order.
+    [cap,2,2] float64, with postprocess also pp_counts [cap,5], pp_rows [cap,3,4] int64 and pp_bits / pp_aux_bits [cap,words] on `device`, one row per image
+    in update() order.
     update() enqueues kernels and returns -- the row offset and the images' domains are host integers; result() is the one call that copies to the host.
     The tables double when they are full (a stream-ordered device copy); `capacity` = the epoch's image count avoids that."""
 
     def __init__(self, num_domains: int = 4, device=None, masks: bool = False, aux_masks: bool = False, structure: bool = False, capacity: int = 0,
-                 boundary: bool = False):
+                 boundary: bool = False, postprocess=None):
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         device = torch.device(device)
@@ -149,13 +177,16 @@ class ImageReport:
         self.device = device
         self.masks, self.aux_masks, self.structure = bool(masks), bool(aux_masks), bool(structure)
         self.boundary = bool(boundary)
+        self.postprocess = postprocess
+        self._pp_mode = None if postprocess is None else postprocess_mode(postprocess)
         self.capacity = max(int(capacity), 0)
         self.size = None          # (H, W), fixed by the first update
         self.rows = 0
         self.domains: list = []
         self.counts = self.structure_col = self.bits = self.aux_bits = self.boundary_rows = self.boundary_sums = None
+        self.pp_counts = self.pp_rows = self.pp_bits = self.pp_aux_bits = None
         self._cap = 0
-        self._ws = self._ws_s = self._ws_b = None
+        self._ws = self._ws_s = self._ws_b = self._ws_c = None
 
     def reset(self):
         """forget the images (the tables, their capacity and the image size stay)"""
@@ -184,6 +215,13 @@ class ImageReport:
         if self.boundary:
             self.boundary_rows = self._table(self.boundary_rows, cap, (2, _BOUNDARY_COLUMNS), torch.int64)
             self.boundary_sums = self._table(self.boundary_sums, cap, (2, 2), torch.float64)
+        if self._pp_mode is not None:
+            self.pp_counts = self._table(self.pp_counts, cap, (_COUNT_COLUMNS,), torch.int64)
+            self.pp_rows = self._table(self.pp_rows, cap, _PP_ROW, torch.int64)
+            if self.masks:
+                self.pp_bits = self._table(self.pp_bits, cap, (words,), torch.int64)
+            if self.aux_masks:
+                self.pp_aux_bits = self._table(self.pp_aux_bits, cap, (words,), torch.int64)
         self._cap = cap
 
     @staticmethod
@@ -218,6 +256,11 @@ class ImageReport:
                 raise ValueError(f"boundary=True needs [B,1,H,W] or [B,H,W] logits, got {tuple(out.shape)}")
             if max(size) > _BOUNDARY_MAX_SIDE:
                 raise ValueError(f"boundary=True takes images up to {_BOUNDARY_MAX_SIDE} x {_BOUNDARY_MAX_SIDE}, got {size[0]} x {size[1]}")
+        if self._pp_mode is not None:
+            if not ((out.dim() == 4 and out.shape[1] == 1) or out.dim() == 3):
+                raise ValueError(f"postprocess needs [B,1,H,W] or [B,H,W] logits, got {tuple(out.shape)}")
+            if max(size) > _PP_MAX_SIDE:
+                raise ValueError(f"postprocess takes images up to {_PP_MAX_SIDE} x {_PP_MAX_SIDE}, got {size[0]} x {size[1]}")
         if self.size is None:
             self.size = size
         elif size != self.size:
@@ -245,6 +288,17 @@ class ImageReport:
             if self._ws_b is None:
                 self._ws_b = torch.empty(((nbytes + 7) // 8,), device=self.device, dtype=torch.int64)
             ops.eval_boundary(out, aux, label, self.boundary_rows[r0:r1], self.boundary_sums[r0:r1], self._ws_b)
+        if self._pp_mode is not None:
+            nbytes = ops.eval_components_ws_bytes(n, size[0], size[1])
+            self._ws_c = self._workspace(self._ws_c, nbytes)
+            if self._ws_c is None:
+                self._ws_c = torch.empty(((nbytes + 7) // 8,), device=self.device, dtype=torch.int64)
+            pp_aux_bits = self.pp_aux_bits[r0:r1] if self.aux_masks else None
+            if aux is None and pp_aux_bits is not None:
+                pp_aux_bits.zero_()
+                pp_aux_bits = None
+            ops.eval_components(out, aux, label, self._pp_mode, self.pp_counts[r0:r1], self.pp_rows[r0:r1], self._ws_c,
+                                self.pp_bits[r0:r1] if self.masks else None, pp_aux_bits)
         for d, k in zip(domains, images):
             self.domains.extend([d] * k)
         self.rows = r1
@@ -256,7 +310,10 @@ class ImageReport:
         (scores_from_counts), "structure" float64 [N], "masks" / "aux_masks" uint64 [N,words] (unpack_masks) when asked for, "size" (H, W), "per_domain"
         {domain: images, dice_mean, dice_std, iou_mean, iou_std, structure_loss} and "sum_structure_loss".  With boundary=True also boundary_from_rows'
         columns ("hd95", "hd", "assd", "asd_pred_to_label", "asd_label_to_pred", "boundary_valid" and their aux_ twins; NaN where a mask is empty), its
-        per-domain keys inside "per_domain" and "boundary_rows", the raw int64 table [N,2,6]."""
+        per-domain keys inside "per_domain" and "boundary_rows", the raw int64 table [N,2,6].  With postprocess also postprocess_from_rows' columns
+    ("pp_counts", "pp_dice", "pp_iou", "pp_aux_dice", "pp_aux_iou", "components", "largest_area", "filled", "removed"), its per-domain keys
+    (pp_dice_mean, pp_dice_std, pp_iou_mean, pp_iou_std), "pp_masks" / "pp_aux_masks" (the cleaned masks, when masks / aux_masks are on) and
+    "postprocess", the mode."""
         N = self.rows
         parts = []          # (name, dtype, shape)
         if N:
@@ -270,6 +327,13 @@ class ImageReport:
             if self.boundary:
                 tabs.append(("boundary_rows", self.boundary_rows, np.int64))
                 tabs.append(("boundary_sums", self.boundary_sums, np.float64))
+            if self._pp_mode is not None:
+                tabs.append(("pp_counts", self.pp_counts, np.int64))
+                tabs.append(("pp_rows", self.pp_rows, np.int64))
+                if self.masks:
+                    tabs.append(("pp_masks", self.pp_bits, np.uint64))
+                if self.aux_masks:
+                    tabs.append(("pp_aux_masks", self.pp_aux_bits, np.uint64))
             dev = torch.cat([t[:N].reshape(-1).view(torch.uint8) for _, t, _ in tabs])          # every table is 8-byte elements: the offsets stay aligned
             host = torch.empty((dev.numel(),), dtype=torch.uint8, pin_memory=True)
             host.copy_(dev, non_blocking=True)
@@ -294,4 +358,14 @@ class ImageReport:
                 res["per_domain"][d].update(row)
             res.update(b)
             res["boundary_rows"] = rows
+        if self._pp_mode is not None:
+            pp = postprocess_from_rows(got.get("pp_counts", np.zeros((0, _COUNT_COLUMNS), dtype=np.int64)),
+                                       got.get("pp_rows", np.zeros((0,) + _PP_ROW, dtype=np.int64)), res["domain"])
+            for d, row in pp.pop("per_domain").items():
+                res["per_domain"][d].update(row)
+            res.update(pp)
+            for name, on in (("pp_masks", self.masks), ("pp_aux_masks", self.aux_masks)):
+                if on:
+                    res[name] = got.get(name, np.zeros((0, words), dtype=np.uint64))
+            res["postprocess"] = self.postprocess
         return res
