@@ -740,6 +740,24 @@ int mdvit_eval_components(const float* out, const float* aux, const float* label
 size_t mdvit_label_components_ws_bytes(int32_t n, int32_t H, int32_t W);
 int mdvit_label_components(const uint8_t* masks, int32_t n, int32_t H, int32_t W, int32_t* labels, int64_t* components, void* ws, size_t ws_bytes,
                            void* stream);
+/* Signed distance map of the labels, for the boundary loss (Kervadec et al., MIDL 2019: one_hot2dist on one 2-D image at a time).  label [n][H][W] fp32,
+ * pos = label != 0 (mdvit_eval_images' predicate).  d2: the exact integer squared Euclidean distance of a pixel to the nearest pixel of the OTHER class (for a
+ * background pixel the nearest foreground pixel, for a foreground pixel the nearest background pixel); in fp32  r = sqrtf((float)d2),  phi = pos ? 1 - r : r
+ * -- 0 on foreground pixels that touch the background, negative inside, >= 1 outside:  edt(~pos) * ~pos - (edt(pos) - 1) * pos.  An image with one class only
+ * (an empty or a full label) has d2 = 0 and phi = 0 everywhere.  phi [n][H][W] fp32; d2 [n][H][W] int32, nullable.  Every element of the outputs is written
+ * on every call; integer work up to sqrtf (correctly rounded: d2 < 2^21 is an exact fp32 integer), no atomics: a call is bit-reproducible.  Enqueue only.
+ * MDVIT_E_SHAPE for a NULL label / phi, n outside 1..65535 or H or W outside 1..1024; mdvit_signed_distance_ws_bytes returns 0 for the same sizes.  ws: that
+ * many bytes, 8-byte aligned (MDVIT_E_ALIGN); a short one is MDVIT_E_WORKSPACE.  All refusals come before any launch. */
+size_t mdvit_signed_distance_ws_bytes(int32_t n, int32_t H, int32_t W);
+int mdvit_signed_distance(const float* label, int32_t n, int32_t H, int32_t W, float* phi, int32_t* d2, void* ws, size_t ws_bytes, void* stream);
+/* Boundary loss on 1-channel logits [n][hw] and a map phi of the same shape:  L = sum over the `groups` equal consecutive domain batches of
+ * mean_batch(sigmoid(x) * phi)  (groups = 1: the mean over everything), written to loss[0] on the device.  Per-workgroup fp64 partial sums in ws
+ * (mdvit_boundary_loss_ws_bytes, 8-byte aligned), then one fixed-order second stage: no atomics, bit-reproducible.  The backward is element-wise:
+ * dlogits = gout[0] * phi * s (1 - s) / (n / groups * hw) -- rounded as (((g (1 / N)) phi) (1 - s)) s, the order of torch's autograd --, the upstream gradient read from DEVICE memory; phi receives no gradient.  MDVIT_E_SHAPE for a NULL
+ * pointer, n or hw < 1, hw > 1024 * 1024, groups outside 1..64 or not a divisor of n (the ws query returns 0 there); MDVIT_E_WORKSPACE / MDVIT_E_ALIGN as above. */
+size_t mdvit_boundary_loss_ws_bytes(int64_t n, int64_t hw, int32_t groups);
+int mdvit_boundary_loss_fwd(const float* logits, const float* phi, int64_t n, int64_t hw, int32_t groups, float* loss, void* ws, size_t ws_bytes, void* stream);
+int mdvit_boundary_loss_bwd(const float* logits, const float* phi, const float* gout, int64_t n, int64_t hw, int32_t groups, float* dlogits, void* stream);
 /* uint8 HWC image [B,H,W,3] -> fp32 CHW [B,3,H,W]:  ((float)(u8 / 255.0) - mean[c]) / std[c]  with the ImageNet mean / std
  * (create_dataset.py:25-26 norm01, :143-144,165-172 permute + transforms.Normalize), bit-exact with that sequence. */
 int mdvit_image_normalize_u8(const uint8_t* img_nhwc, float* out_nchw, int32_t B, int32_t H, int32_t W, void* stream);

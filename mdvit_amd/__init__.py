@@ -1,7 +1,7 @@
 """mdvit_amd -- MI355X-native (gfx950 HIP) forward/backward path of MDViT behind the reference's
 nn.Module call surface.  See DESIGN.md / INTEGRATION.md."""
 from .model import BASE, BASE_DASE, BASE_DSN, BASE_USE, MDViT, MDViT_DSN  # noqa: F401
-from .losses import domain_losses, seg_loss  # noqa: F401
+from .losses import boundary_loss, domain_losses, seg_loss, signed_distance  # noqa: F401
 from .evaluate import EvalAccumulator, evaluate  # noqa: F401
 from .report import ImageReport, unpack_masks  # noqa: F401
 from .data import DeviceDataset, DomainBatches  # noqa: F401
@@ -18,5 +18,5 @@ def load_reference_state_dict(model, state_dict, strict: bool = True):
     return model.load_state_dict(sd, strict=strict)
 
 
-__all__ = ["MDViT", "MDViT_DSN", "BASE", "BASE_DSN", "BASE_DASE", "BASE_USE", "SwinUnet", "UTNet", "domain_losses", "seg_loss", "load_reference_state_dict",
+__all__ = ["MDViT", "MDViT_DSN", "BASE", "BASE_DSN", "BASE_DASE", "BASE_USE", "SwinUnet", "UTNet", "domain_losses", "seg_loss", "boundary_loss", "signed_distance", "load_reference_state_dict",
            "EvalAccumulator", "evaluate", "ImageReport", "unpack_masks", "DeviceDataset", "DomainBatches", "DeviceSnapshot", "TrainState"]

@@ -251,6 +251,9 @@ _SIGS = {
     "mdvit_eval_boundary": [vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_size_t, vp],
     "mdvit_eval_components": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, vp],
     "mdvit_label_components": [vp, i32, i32, i32, vp, vp, vp, C.c_size_t, vp],
+    "mdvit_signed_distance": [vp, i32, i32, i32, vp, vp, vp, C.c_size_t, vp],
+    "mdvit_boundary_loss_fwd": [vp, vp, i64, i64, i32, vp, vp, C.c_size_t, vp],
+    "mdvit_boundary_loss_bwd": [vp, vp, vp, i64, i64, i32, vp, vp],
     "mdvit_image_normalize_u8": [vp, vp, i32, i32, i32, vp],
     "mdvit_augment_normalize_u8": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "mdvit_augment_probe_taps": [f32, f32, i32, i32, C.POINTER(i32), C.POINTER(f32)],
@@ -374,6 +377,10 @@ def _attach_prototypes(lib):
     lib.mdvit_eval_components_ws_bytes.argtypes = [i32, i32, i32]
     lib.mdvit_label_components_ws_bytes.restype = C.c_size_t
     lib.mdvit_label_components_ws_bytes.argtypes = [i32, i32, i32]
+    lib.mdvit_signed_distance_ws_bytes.restype = C.c_size_t
+    lib.mdvit_signed_distance_ws_bytes.argtypes = [i32, i32, i32]
+    lib.mdvit_boundary_loss_ws_bytes.restype = C.c_size_t
+    lib.mdvit_boundary_loss_ws_bytes.argtypes = [i64, i64, i32]
     lib.mdvit_winattn_bwd_ws_bytes.restype = C.c_size_t
     lib.mdvit_winattn_bwd_ws_bytes.argtypes = [i32, i32, i32, i32]
     lib.mdvit_lrattn_bwd_ws_bytes.restype = C.c_size_t

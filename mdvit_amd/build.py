@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libmdvit_hip.so")
-SOURCES = ["abi.hip", "gemm.hip", "gemm_tn.hip", "gemm_bp.hip", "gemm_ph.hip", "gemm_pm.hip", "mlp.hip", "mlp_rc.hip", "block.hip", "norm.hip", "conv.hip", "attn.hip", "loss.hip", "optim.hip", "transfuse.hip", "sdpa.hip", "winattn.hip", "swin_norm.hip", "lowrank_attn.hip", "pool.hip", "se_adapter.hip", "augment.hip", "evaluate.hip", "eval_images.hip", "eval_boundary.hip", "eval_components.hip", "dataset.hip", "snapshot.hip"]
+SOURCES = ["abi.hip", "gemm.hip", "gemm_tn.hip", "gemm_bp.hip", "gemm_ph.hip", "gemm_pm.hip", "mlp.hip", "mlp_rc.hip", "block.hip", "norm.hip", "conv.hip", "attn.hip", "loss.hip", "optim.hip", "transfuse.hip", "sdpa.hip", "winattn.hip", "swin_norm.hip", "lowrank_attn.hip", "pool.hip", "se_adapter.hip", "augment.hip", "evaluate.hip", "eval_images.hip", "eval_boundary.hip", "eval_components.hip", "signed_distance.hip", "dataset.hip", "snapshot.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # per-file extras.  -fno-slp-vectorize: hipcc's SLP pass packs adjacent scalar f32 adds / muls of an activation into v_pk_* instructions,
 # which next to MFMAs cost ~20 cycles more than the two plain VALU they replace (MI355X_MICROARCH.md, per-instruction constants)

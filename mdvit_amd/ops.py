@@ -3544,6 +3544,83 @@ def seg_losses(out, aux, label):
     return _SegLosses.apply(_c(out), None if aux is None else _c(aux), _c(label.float()))
 
 
+SD_MAX_SIDE = 1024          # mdvit_signed_distance: d^2 <= 2 * 1023^2 < 2^21 stays an exact fp32 integer
+
+
+def _image_dims(t, what):
+    """(n, H, W) of a batch of 1-channel images [n,1,H,W] or [n,H,W]; ValueError for anything else or a side the distance kernels do not take"""
+    if not (t.dim() == 3 or (t.dim() == 4 and t.shape[1] == 1)) or t.numel() == 0:
+        raise ValueError(f"{what} expects [B,1,H,W] or [B,H,W] (got {tuple(t.shape)})")
+    H, W = int(t.shape[-2]), int(t.shape[-1])
+    if H > SD_MAX_SIDE or W > SD_MAX_SIDE:
+        raise ValueError(f"{what}: images up to {SD_MAX_SIDE} x {SD_MAX_SIDE} (got {H} x {W})")
+    return int(t.shape[0]), H, W
+
+
+def signed_distance_ws_bytes(n: int, H: int, W: int) -> int:
+    """bytes of mdvit_signed_distance's workspace for n images of H x W pixels (0 for sizes the entry refuses)"""
+    return int(_lib.load().mdvit_signed_distance_ws_bytes(int(n), int(H), int(W)))
+
+
+def signed_distance(label, return_squared: bool = False):
+    """The signed distance map of the boundary loss (Kervadec et al., MIDL 2019, one_hot2dist), image by image and on the device: label [B,1,H,W] or [B,H,W]
+    (pos = label != 0) -> phi fp32 in the label's shape: sqrt(d2) on the background, 1 - sqrt(d2) on the foreground, d2 the exact squared distance to the nearest
+    pixel of the other class; zeros for an image whose label is empty or full.  return_squared: also d2 as int32.  H, W <= 1024.  No gradient, no sync."""
+    n, H, W = _image_dims(label, "signed_distance")
+    with torch.no_grad():
+        lab = _c(label.detach().float())
+        _chk(lab)
+        phi = _empty_like(lab)
+        d2 = torch.empty(lab.shape, device=lab.device, dtype=torch.int32) if return_squared else None
+        nbytes = signed_distance_ws_bytes(n, H, W)
+        ws = torch.empty((nbytes // 8,), device=lab.device, dtype=torch.int64)
+        call("mdvit_signed_distance", _p(lab), n, H, W, _p(phi), _p(d2), _p(ws), nbytes, _stream())
+    return (phi, d2) if return_squared else phi
+
+
+class _BoundaryLoss(torch.autograd.Function):
+    """mean(sigmoid(x) * phi) per domain batch, summed over the batches; phi is a constant of the graph"""
+
+    @staticmethod
+    def forward(ctx, logits, phi, groups):
+        n, hw = logits.shape[0], logits.shape[-2] * logits.shape[-1]
+        nbytes = int(_lib.load().mdvit_boundary_loss_ws_bytes(n, hw, groups))
+        ws = _empty((nbytes // 8,), device=logits.device, dtype=torch.float64)
+        loss = _empty((1,), device=logits.device, dtype=torch.float32)
+        call("mdvit_boundary_loss_fwd", _p(logits), _p(phi), n, hw, groups, _p(loss), _p(ws), nbytes, _stream())
+        ctx.groups = groups
+        ctx.save_for_backward(logits, phi)
+        ctx.set_materialize_grads(False)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, phi = ctx.saved_tensors
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        g = _c(g.reshape(()).float())
+        dlogits = _empty_like(logits)
+        call("mdvit_boundary_loss_bwd", _p(logits), _p(phi), _p(g), logits.shape[0], logits.shape[-2] * logits.shape[-1], ctx.groups, _p(dlogits), _stream())
+        return dlogits, None, None
+
+
+def boundary_loss(logits, phi, groups: int = 1):
+    """Boundary loss (Kervadec et al., MIDL 2019) of 1-channel logits [B,1,H,W] or [B,H,W] on a map phi of the same shape (signed_distance): a 0-dim tensor,
+    (1 / (B H W)) sum sigmoid(x) phi, differentiable w.r.t. the logits only.  groups = G: the B images are G equal consecutive domain batches, the result the sum
+    of their G means."""
+    n, H, W = _image_dims(logits, "boundary_loss")
+    if tuple(phi.shape) != tuple(logits.shape):
+        raise ValueError(f"boundary_loss: logits {tuple(logits.shape)} and phi {tuple(phi.shape)} disagree")
+    groups = int(groups)
+    if groups < 1 or groups > 64 or n % groups:
+        raise ValueError(f"boundary_loss: batch {n} is not {groups} equal domain batches (1..64)")
+    if logits.dtype != torch.float32 or phi.dtype != torch.float32:
+        raise ValueError(f"boundary_loss: logits and phi are fp32 (got {logits.dtype}, {phi.dtype})")
+    logits, phi = _c(logits), _c(phi.detach())
+    _chk(logits, phi)
+    return _BoundaryLoss.apply(logits, phi, groups)
+
+
 # ------------------------------------------------------------------------------------------------
 # on-device metrics and input pipeline (no autograd)
 # ------------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .losses import domain_losses, seg_loss
+from .losses import boundary_loss, domain_losses, seg_loss
 from .parallel import GradAccumulator, GradBucketReducer
 
 
@@ -58,14 +58,17 @@ def mdvit_train_step(model, batches: Sequence[tuple], optimizer=None, alpha: flo
                      reducer: Optional[GradBucketReducer] = None, per_domain_backward: bool = True,
                      use_domain_label: bool = True, accumulator: Optional[GradAccumulator] = None,
                      merged_sweeps: bool = False, fuse_domains: int = 1, phase_events: Optional[list] = None,
-                     with_metrics: bool = False) -> Dict[str, torch.Tensor]:
+                     with_metrics: bool = False, boundary_weight: float = 0.0) -> Dict[str, torch.Tensor]:
     """batches: [(img (B,3,H,W), label (B,1,H,W), set_id (B,) int64)] one per domain.
     Returns the summed losses as device tensors (no host sync inside the step).
     accumulator: fused gradient accumulation (+ overlapped all-reduce when world_size > 1), see parallel.GradAccumulator.
     merged_sweeps: same gradients as the reference's two sweeps with half the weight-gradient work.  Back-propagation
       is linear in the upstream gradient, so  grad(aux, adapters frozen) + grad(uni)  ==  grad(aux + uni) - [adapter part of
       grad(aux)].  Sweep 1 therefore runs data-gradients-only (no wgrad GEMMs / reductions) and hands every domain adapter
-      MINUS its aux gradient; sweep 2 is one ordinary backward of aux + uni."""
+      MINUS its aux gradient; sweep 2 is one ordinary backward of aux + uni.
+    boundary_weight w > 0: the main output's loss is l + w * L_B(out), L_B the boundary loss (losses.boundary_loss) on the signed distance map of this forward's
+      labels (one map per forward, after augmentation) -- uni = alpha * kt + (1 - alpha) * (l + w * L_B); the auxiliary loss and its sweep are untouched.  The
+      result gains "boundary_loss" (L_B summed over the domains; "loss" stays the region loss l).  0 (the default): nothing of it is launched or allocated."""
     da = _da_params(model)
     fused_forward = fuse_domains > 1 and len(batches) > 0 and fuse_domains >= len(batches)       # one forward per step: every module is used once
     ops.refresh_transposes()          # the W^T copies of the bf16x3 data-gradient GEMMs follow the last optimizer update (one launch)
@@ -162,7 +165,7 @@ def mdvit_train_step(model, batches: Sequence[tuple], optimizer=None, alpha: flo
             e.record()
             phase_events.append((tag, e))
 
-    tot = tot_aux = tot_kt = None
+    tot = tot_aux = tot_kt = tot_b = None
     stash = []
     metric_rows = []        # per domain [dice, iou, aux dice, aux iou] of the thresholded outputs, kept on the device
     mark("start")
@@ -186,6 +189,12 @@ def mdvit_train_step(model, batches: Sequence[tuple], optimizer=None, alpha: flo
             for g in range(G):
                 metric_rows.append(ops.seg_metrics(out[g * Bd:(g + 1) * Bd], None if aux is None else aux[g * Bd:(g + 1) * Bd],
                                                    label[g * Bd:(g + 1) * Bd])[0])
+        if boundary_weight:
+            # `out` gets a second consumer in the full sweep: its two gradients are added by ops.fork (ours, on the sweep's stream), not by the engine.  The
+            # boundary node is not reachable from the aux loss, so the aux sweep's graph audit (_aux_graph_is_ours) sees one consumer of the fork as before
+            out, out_b = ops.fork(out, 2)
+            lb = boundary_loss(out_b, label, phi=ops.signed_distance(label), groups=G)
+            tot_b = lb.detach() if tot_b is None else tot_b + lb.detach()
         if G == 1:
             l, la, lk = domain_losses(out, aux, label)
         else:       # per-domain BCE/Dice/KT (each a mean over ITS batch, multi_train_MDViT.py:147-153), then summed
@@ -198,6 +207,8 @@ def mdvit_train_step(model, batches: Sequence[tuple], optimizer=None, alpha: flo
         tot = l.detach() if tot is None else tot + l.detach()
         tot_aux = la.detach() if tot_aux is None else tot_aux + la.detach()
         tot_kt = lk.detach() if tot_kt is None else tot_kt + lk.detach()
+        if boundary_weight:
+            l = l + boundary_weight * lb
         mark("fwd")
         if per_domain_backward:
             two_sweeps(la, alpha * lk + (1 - alpha) * l, last=(i == len(batches) - 1))
@@ -216,6 +227,8 @@ def mdvit_train_step(model, batches: Sequence[tuple], optimizer=None, alpha: flo
     res = {"loss": tot, "aux_loss": tot_aux, "kt_loss": tot_kt}
     if with_metrics:
         res["metrics"] = torch.stack(metric_rows)          # [domains, 4]
+    if boundary_weight:
+        res["boundary_loss"] = tot_b
     return res
 
 
@@ -299,10 +312,12 @@ def _fuse_batches(batches, fuse_domains, num_domains, use_domain_label):
 
 def base_train_step(model, batches: Sequence[tuple], optimizer=None, reducer: Optional[GradBucketReducer] = None,
                     num_domains: int = 4, use_domain_label: bool = False,
-                    accumulator: Optional[GradAccumulator] = None, fuse_domains: int = 1) -> Dict[str, torch.Tensor]:
+                    accumulator: Optional[GradAccumulator] = None, fuse_domains: int = 1, boundary_weight: float = 0.0) -> Dict[str, torch.Tensor]:
     """multi_train_BASE.py:150-200: per domain loss = BCE + Dice, one backward of the sum.
     fuse_domains > 1 (models whose forward takes `groups`: BASE_DASE / BASE_USE): runs of up to that many equally shaped domain batches go through ONE
-    forward, model(img, groups=G) -- BatchNorm statistics per domain batch, the losses per domain batch and summed: the same step as one forward per domain."""
+    forward, model(img, groups=G) -- BatchNorm statistics per domain batch, the losses per domain batch and summed: the same step as one forward per domain.
+    boundary_weight w > 0: the loss is seg_loss + w * L_B (losses.boundary_loss on the map of this forward's labels); the result gains "boundary_loss", "loss"
+    stays the region loss.  0 (the default): nothing of it is launched or allocated."""
     ops.refresh_transposes()          # cached W^T / weight planes follow the last optimizer update (one launch each)
     if accumulator is not None:
         accumulator.zero()
@@ -312,7 +327,7 @@ def base_train_step(model, batches: Sequence[tuple], optimizer=None, reducer: Op
         optimizer.zero_grad(set_to_none=True)
     else:
         model.zero_grad(set_to_none=True)
-    tot = None
+    tot = tot_b = None
     if fuse_domains > 1:
         if use_domain_label:
             raise ValueError("base_train_step: fuse_domains is for the models that take no domain label")
@@ -325,6 +340,10 @@ def base_train_step(model, batches: Sequence[tuple], optimizer=None, reducer: Op
             out = model(img, groups=G)
         else:
             out = model(img)
+        if boundary_weight:
+            out, out_b = ops.fork(out, 2)          # two consumers of `out`: their gradients are added by ops.fork
+            lb = boundary_loss(out_b, label, phi=ops.signed_distance(label), groups=G)
+            tot_b = lb.detach() if tot_b is None else tot_b + lb.detach()
         if G > 1:
             Bd = img.shape[0] // G
             og = ops.split_groups(out, G)
@@ -336,7 +355,7 @@ def base_train_step(model, batches: Sequence[tuple], optimizer=None, reducer: Op
             accumulator.begin_sweep(last)
         elif reducer is not None and last:
             reducer.arm()
-        _backward(l)
+        _backward(l + boundary_weight * lb if boundary_weight else l)
         ops.join_side_stream()
         if accumulator is not None:
             accumulator.end_sweep(last)
@@ -345,4 +364,4 @@ def base_train_step(model, batches: Sequence[tuple], optimizer=None, reducer: Op
         reducer.finish()
     if optimizer is not None:
         optimizer.step()
-    return {"loss": tot}
+    return {"loss": tot, "boundary_loss": tot_b} if boundary_weight else {"loss": tot}
